@@ -12,7 +12,12 @@ Nominal work per step: frames*tracks*candidates for PreSync +
 frames*tracks per Sync outer iteration.  value = nominal ray-residuals of all
 GPUs / wall time (max over ranks); inputs are resident in HBM before timing.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the JSON line (with the per-kernel times and rooflines
+of the timed steps' own HIP events).  --full adds the untimed extras after it: the CPU baseline, the HIP-vs-oracle
+parity check on its sample and the reference-driver workload.  --dump-outputs DIR writes what the last timed step
+returned as DIR/<name>.npy (float64; the inputs are seeded, so two builds compare output for output).
 
 N > 1 needs no external launcher.  Two ways of using N GPUs (the reference parallelises over frames inside one
 object, core_private.cpp:73,231,245,263):
@@ -66,7 +71,13 @@ def parse_args(argv=None):
     ap.add_argument("--search-step", type=float, default=0.0005)
     ap.add_argument("--search-radius", type=float, default=0.2)
     ap.add_argument("--outer-iters", type=int, default=20)
-    ap.add_argument("--cpu-frames", type=int, default=192, help="frames of the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the untimed extras: the CPU baseline, the parity check and the "
+                         "reference-driver workload (off by default: a plain run does only what the headline figure needs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (PreSync's and Sync's cost and delay, Sync's trace; "
+                         "with --workload c5 the sweep's costs and delays) as DIR/<name>.npy in float64")
+    ap.add_argument("--cpu-frames", type=int, default=192, help="frames of the CPU-baseline sample (0 = skip; --full only)")
     ap.add_argument("--mode", default="ranks", choices=["ranks", "inproc"],
                     help="ranks: one process per GPU (self-spawned unless WORLD_SIZE is set); inproc: one object "
                          "driving all GPUs of this process")
@@ -76,9 +87,9 @@ def parse_args(argv=None):
                          "host transport; bit-identical to the host loop (tests/test_gpu_parity.py, two ranks)")
     ap.add_argument("--no-hook-device-loop", dest="hook_device_loop", action="store_false",
                     help="with --exchange torch: Sync's loop on the host, one hook call per launch")
-    ap.add_argument("--no-parity", action="store_true", help="skip the untimed HIP-vs-oracle comparison on the CPU sample")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the untimed HIP-vs-oracle comparison on the CPU sample")
     ap.add_argument("--no-driver-workload", action="store_true",
-                    help="skip the (untimed) reference-driver workload: 98 sync points of 61 x 130, PreSync + 4 x Sync each "
+                    help="with --full: skip the (untimed) reference-driver workload: 98 sync points of 61 x 130, PreSync + 4 x Sync each "
                          "(core_testcode.cpp:270-316), with its CPU sample and its critical-path bound")
     ap.add_argument("--driver-cpu-positions", type=int, default=16, help="sync points of the driver workload the oracle is timed on")
     ap.add_argument("--exchange", default="torch", choices=["native", "torch"],
@@ -264,6 +275,7 @@ def run(args):
 
     iters_done = []
     result = {}
+    outputs = {}  # what the last step returned to its caller (--dump-outputs)
 
     def step():
         if c5:
@@ -274,14 +286,17 @@ def run(args):
             order = np.argsort(costs)
             result.update(best_orientation=orient_names[int(order[0])], best_delay=float(delays[order[0]]),
                           cost_ratio_best_to_second=float(costs[order[0]] / costs[order[1]]) if len(order) > 1 else None)
+            outputs.update(orientation_costs=costs, orientation_delays=delays)
             iters_done.append(0)
             return 0.0
         ta = time.perf_counter()
         c0, d0 = prob.PreSync(0.0, w_begin, w_end, args.search_step, args.search_radius)
         tb = time.perf_counter() - ta
         c1, d1 = prob.Sync(d0, w_begin, w_end - 1, 0.0, args.search_radius)
-        iters_done.append(len(prob.sync_trace()))
+        trace = prob.sync_trace()
+        iters_done.append(len(trace))
         result.update(presync_delay=d0, presync_cost=c0, sync_delay=d1, sync_cost=c1)
+        outputs.update(presync=(c0, d0), sync=(c1, d1), sync_trace=trace)
         return tb
 
     for _ in range(args.warmup):
@@ -308,6 +323,8 @@ def run(args):
         t = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outputs)
 
     # candidates exactly as the reference's double loop produces them (core_private.cpp:69-70)
     n_cand = 0
@@ -425,12 +442,12 @@ def run(args):
                     break
         kernels = {k: {"launches": v[0], "total_ms": round(v[1], 3)} for k, v in prof.items()}
         cpu = parity = driver = None
-        if n_gpus == 1 and args.cpu_frames > 0 and not c5:
+        if args.full and n_gpus == 1 and args.cpu_frames > 0 and not c5:
             cpu = cpu_baseline(gyro, min(args.cpu_frames, F), N, args)
             if not args.no_parity and not rehearsal:
                 parity = parity_check(gyro, min(args.cpu_frames, F), N, args, cpu.pop("_oracle"))
             cpu.pop("_oracle", None)
-        if n_gpus == 1 and not c5 and not rehearsal and not args.no_driver_workload:
+        if args.full and n_gpus == 1 and not c5 and not rehearsal and not args.no_driver_workload:
             del prob                      # (its 1.3 GB of frames are not needed any more)
             driver = driver_workload(args)
         out = {
@@ -499,6 +516,13 @@ def run(args):
         if exchange == "native-rccl":
             prob.rccl_shutdown()
         dist.destroy_process_group()
+
+
+def dump_outputs(out_dir, outputs):
+    """DIR/<name>.npy in float64 for every array the last timed step returned (a few KB in all)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, val in outputs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(val, dtype=np.float64))
 
 
 def host_cores():

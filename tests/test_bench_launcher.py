@@ -123,6 +123,34 @@ def test_eight_ranks_rehearsed_on_the_cpu_stand_in(hosttest_lib):
     assert d["result"]["sync_delay"] == pytest.approx(a["result"]["sync_delay"], abs=1e-9)
 
 
+def test_dump_outputs_and_full(hosttest_lib, tmp_path):
+    """--dump-outputs DIR writes what the last timed step returned, the same on every run with the same arguments; a plain
+    run leaves the CPU baseline to --full, which still runs it."""
+    import numpy as np
+    lib = _lib(hosttest_lib)
+    runs = []
+    for i in range(2):
+        d = tmp_path / ("out%d" % i)
+        rc, out, err = _run([sys.executable, "bench.py", "--gpus", "1", "--frames", "16", "--rehearse-cpu", lib,
+                             "--dump-outputs", str(d)] + SMALL)
+        assert rc == 0 and len(out) == 1, err
+        runs.append((json.loads(out[0]), {p.stem: np.load(p) for p in d.glob("*.npy")}))
+    (line, arrs), (_, arrs2) = runs
+    assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["cpu_baseline"] is None
+    assert sorted(arrs) == ["presync", "sync", "sync_trace"]
+    assert all(a.dtype == np.float64 for a in arrs.values())
+    assert tuple(arrs["presync"]) == (line["result"]["presync_cost"], line["result"]["presync_delay"])
+    assert tuple(arrs["sync"]) == (line["result"]["sync_cost"], line["result"]["sync_delay"])
+    assert len(arrs["sync_trace"]) == line["config"]["sync_outer_iters"][-1]
+    for k in arrs:
+        assert np.array_equal(arrs[k], arrs2[k]), k
+    i = SMALL.index("--cpu-frames")
+    rc, out, err = _run([sys.executable, "bench.py", "--gpus", "1", "--frames", "16", "--rehearse-cpu", lib, "--full"]
+                        + SMALL[:i] + ["--cpu-frames", "8"] + SMALL[i + 2:])
+    assert rc == 0 and len(out) == 1, err
+    assert json.loads(out[0])["cpu_baseline"]["value"] > 0
+
+
 def test_the_line_names_rccl_whenever_the_backend_is_nccl():
     """`rccl_ranks` = the world size whenever RCCL carries the sums -- through the library's own communicator or through
     torch.distributed behind the reduce hook (the default): round 4's line said 0 for an 8-rank RCCL run through the hook.

@@ -1,6 +1,7 @@
 """CPU-side checks of the drop-in boundary: the library loads, exports every symbol the headers
 declare plus the reference's C++ symbols, and refuses loudly to run without a HIP device."""
 import ctypes
+import json
 import os
 import re
 import subprocess
@@ -68,22 +69,29 @@ int main() {
 """
 
 
-REFERENCE_PUBLIC = "/root/reference/src/core/public"  # present in the build container only
+def _interface_digest(path):
+    """sha256 of a header's public interface: from `class ISyncProblem` to the end, comments removed, tokens joined
+    by single spaces (tests/golden/reference_rssync_h.json holds the reference's)."""
+    import hashlib
+    text = open(path).read()
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    body = text[text.index("class ISyncProblem"):]
+    return hashlib.sha256(" ".join(re.findall(r"[A-Za-z_]\w*|\d+|\S", body)).encode()).hexdigest()
 
 
 @pytest.mark.parametrize("header_dir", ["repo", "reference"])
 def test_cxx_client_built_against_the_header_links_and_fails_loudly_without_a_gpu(built, tmp_path, header_dir):
     """A client written against the reference's interface compiles and links unchanged -- against
-    this repo's include/rssync.h and, where the reference checkout is present (the build container),
-    against the reference's OWN src/core/public/rssync.h: that is the drop-in claim.  Without a
+    this repo's include/rssync.h, which declares the reference's src/core/public/rssync.h token for token
+    (the "reference" case: its digest is stored under tests/golden/): that is the drop-in claim.  Without a
     HIP device the library must not compute anything: it follows the reference's panic convention
     (panic.txt + exit status 1, core_support/panic.cpp:7-15)."""
     import torch
     inc = os.path.join(ROOT, "include")
     if header_dir == "reference":
-        if not os.path.exists(os.path.join(REFERENCE_PUBLIC, "rssync.h")):
-            pytest.skip("reference checkout not present on this machine")
-        inc = REFERENCE_PUBLIC
+        ref = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_rssync_h.json")))
+        assert _interface_digest(os.path.join(inc, "rssync.h")) == ref["sha256"]
     src = tmp_path / "client.cpp"
     src.write_text(CLIENT)
     exe = tmp_path / "client"
