@@ -12,3 +12,4 @@ from .problem import SyncProblem, RsSyncError, load_library, library_path  # noq
 from . import synth  # noqa: F401
 from . import dist  # noqa: F401
 from . import quality  # noqa: F401
+from . import track  # noqa: F401

@@ -18,6 +18,8 @@
 //                      between the launches (kernels/syncloop.hpp).
 //   gyro_*, spline_*   the gyro side: integration scan, microsecond-grid resampling, spline
 //                      table (kernels/gyro.hpp).
+//   pyr_down_kernel, lk_kernel  the tracker: image pyramid + sparse pyramidal Lucas-Kanade at the
+//                      driver's grid points (kernels/track.hpp).
 // Data layout and the roofline that bounds each kernel: DESIGN.md.
 // The kernels live in kernels/*.hpp (one header each, included below); this file holds the
 // device context and the launchers.
@@ -40,6 +42,7 @@
 #endif
 
 #include "../../include/rssync_hip.h"
+#include "track_hip.h"
 #include "device_math.hpp"
 #include "sync_math.hpp"
 #include "lens_math.hpp"
@@ -62,6 +65,7 @@ using rs::f4;
 #include "kernels/exec_big.hpp"
 #include "kernels/executor.hpp"
 #include "kernels/gyro.hpp"
+#include "kernels/track.hpp"
 
 // ===========================================================================
 // host side of the C-ABI
@@ -102,6 +106,9 @@ struct rship_ctx {
     // gyro pipeline (rship_gyro_*): inputs, intermediate orientations, grid knots, forward-sweep values, status
     DevBuf g_ts, g_rates, g_us, g_dq, g_q, g_knots, g_cf, g_status;
     uint32_t g_n = 0; // samples of the last rship_gyro_rates_upload
+    // tracker (rship_track_*): two chunk slots (frames + pyramid), the outputs of one call; upload / kernel events per slot
+    DevBuf trk_slot[2], trk_out;
+    hipEvent_t trk_up[2] = {}, trk_k[2] = {};
     int64_t g_first_us = 0, g_last_us = 0;
     std::vector<hipStream_t> loop_streams; // rship_sync_run: one per group of windows
     hipEvent_t loop_ready = nullptr;
@@ -1070,13 +1077,16 @@ void rship_destroy(rship_ctx* c) {
                       &c->plan_idx, &c->plan_chunk_off, &c->plan_win_off, &c->chunk_out, &c->win_out, &c->loop_state, &c->kd, &c->kd64, &c->init_h,
                       &c->frame_cost, &c->best_h, &c->costs, &c->part, &c->flags, &c->stats, &c->redo_mask, &c->redo_delays, &c->redo_count, &c->init_delays64, &c->dump,
                       &c->big_scratch, &c->mo_scratch, &c->mo_evals, &c->mo_order,
-                      &c->g_ts, &c->g_rates, &c->g_us, &c->g_dq, &c->g_q, &c->g_knots, &c->g_cf, &c->g_status};
+                      &c->g_ts, &c->g_rates, &c->g_us, &c->g_dq, &c->g_q, &c->g_knots, &c->g_cf, &c->g_status,
+                      &c->trk_slot[0], &c->trk_slot[1], &c->trk_out};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     if (c->pinned) (void)hipHostFree(c->pinned);
     for (hipStream_t st : c->loop_streams) (void)hipStreamDestroy(st);
     if (c->loop_ready) (void)hipEventDestroy(c->loop_ready);
     if (c->copy_done) (void)hipEventDestroy(c->copy_done);
+    for (hipEvent_t e : {c->trk_up[0], c->trk_up[1], c->trk_k[0], c->trk_k[1]})
+        if (e) (void)hipEventDestroy(e);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
@@ -3056,6 +3066,183 @@ int rship_profile_reset(rship_ctx* c) {
     if (sync_stream(c)) return 1;
     for (int i = 0; i < RSHIP_K_COUNT; ++i) { c->launches[i] = 0; c->total_ms[i] = 0; }
     return 0;
+}
+
+} // extern "C"
+
+// ===========================================================================
+// the tracker (kernels/track.hpp; declared in track_hip.h, called by track_api.cpp)
+
+namespace {
+
+// Device bytes the tracker may hold for frames + pyramids: two chunk slots (the one the kernels read, the one the next
+// upload fills) share it.  Not a knob: a chunk is as many frames as fit, at least a pair.
+constexpr size_t kTrackBudget = 256ull << 20;
+
+struct TrackGeom {
+    TrackLevels L;
+    uint64_t u8_stride = 0, pyr_stride = 0; // bytes / floats per frame
+    uint32_t chunk = 0;                     // frames per chunk slot
+    uint32_t ny = 0, n_points = 0;
+};
+
+int track_geom(rship_ctx* c, const rship_track_cfg* g, TrackGeom* t) {
+    if (!g->width || !g->height || !g->step || g->levels < 1 || g->levels > (uint32_t)kTrackMaxLevels || g->window < 3 ||
+        g->window > (uint32_t)kTrackMaxWin || !(g->window & 1))
+        return set_err(c, "track: bad configuration");
+    t->L = TrackLevels{};
+    uint32_t w = g->width, h = g->height;
+    uint64_t off = 0;
+    for (uint32_t l = 0; l < g->levels; ++l) {
+        if (l) { w = (w + 1) / 2; h = (h + 1) / 2; }
+        if (w < 3 || h < 3) return set_err(c, "track: frame too small for the pyramid");
+        t->L.w[l] = w;
+        t->L.h[l] = h;
+        if (l) { t->L.off[l] = off; off += (uint64_t)w * h; }
+    }
+    t->u8_stride = (uint64_t)g->width * g->height;
+    t->pyr_stride = (off + 63) / 64 * 64;
+    const uint64_t per_frame = t->u8_stride + 4 * t->pyr_stride;
+    t->chunk = (uint32_t)std::max<uint64_t>(2, std::min<uint64_t>(1u << 20, kTrackBudget / 2 / per_frame));
+    t->ny = (g->height - 1) / g->step;
+    t->n_points = ((g->width - 1) / g->step) * t->ny;
+    return 0;
+}
+
+// the frames must be host memory or memory of the context's device: another device's pointer is an error, not a copy
+int track_check_pointer(rship_ctx* c, const void* p) {
+    hipPointerAttribute_t at{};
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return 0; } // pageable host memory
+    if ((at.type == hipMemoryTypeDevice || at.isManaged) && at.device != c->device)
+        return set_err(c, "track: the frames are in memory of device " + std::to_string(at.device) + ", the problem runs on device " +
+                              std::to_string(c->device));
+    return 0;
+}
+
+// frames [f0, f0 + cnt) -> slot (packed, pitch = width), on the copy stream after the slot's previous kernels
+int track_upload(rship_ctx* c, const TrackGeom& t, int slot, bool reused, const uint8_t* frames, uint32_t f0, uint32_t cnt,
+                 size_t pitch, size_t fstride) {
+    uint8_t* dst = (uint8_t*)c->trk_slot[slot].p;
+    const uint32_t w = t.L.w[0], h = t.L.h[0];
+    if (reused) RS_HIP(hipStreamWaitEvent(c->copy_stream, c->trk_k[slot], 0));
+    if (fstride == pitch * h) // one copy for the whole chunk: its rows are equally spaced
+        RS_HIP(hipMemcpy2DAsync(dst, w, frames + (size_t)f0 * fstride, pitch, w, (size_t)h * cnt, hipMemcpyDefault, c->copy_stream));
+    else
+        for (uint32_t i = 0; i < cnt; ++i)
+            RS_HIP(hipMemcpy2DAsync(dst + (size_t)i * t.u8_stride, w, frames + (size_t)(f0 + i) * fstride, pitch, w, h, hipMemcpyDefault,
+                                    c->copy_stream));
+    RS_HIP(hipEventRecord(c->trk_up[slot], c->copy_stream));
+    return 0;
+}
+
+// the pyramid of the slot's first cnt frames, on the context's stream after the slot's upload
+int track_pyramid(rship_ctx* c, const TrackGeom& t, int slot, uint32_t cnt, uint32_t levels) {
+    RS_HIP(hipStreamWaitEvent(c->stream, c->trk_up[slot], 0));
+    const uint8_t* u8 = (const uint8_t*)c->trk_slot[slot].p;
+    float* pyr = (float*)(u8 + (size_t)t.chunk * t.u8_stride);
+    for (uint32_t l = 1; l < levels; ++l) {
+        const dim3 grid((t.L.w[l] + kPyrTW - 1) / kPyrTW, (t.L.h[l] + kPyrTH - 1) / kPyrTH, cnt);
+        float* dst = pyr + t.L.off[l];
+        if (l == 1)
+            hipLaunchKernelGGL(pyr_down_kernel<true>, grid, dim3(256), 0, c->stream, (const void*)u8, (uint64_t)t.u8_stride, (int)t.L.w[0],
+                               (int)t.L.h[0], dst, (uint64_t)t.pyr_stride, (int)t.L.w[1], (int)t.L.h[1]);
+        else
+            hipLaunchKernelGGL(pyr_down_kernel<false>, grid, dim3(256), 0, c->stream, (const void*)(pyr + t.L.off[l - 1]), (uint64_t)t.pyr_stride,
+                               (int)t.L.w[l - 1], (int)t.L.h[l - 1], dst, (uint64_t)t.pyr_stride, (int)t.L.w[l], (int)t.L.h[l]);
+        RS_HIP(hipGetLastError());
+    }
+    return 0;
+}
+
+// geometry, pointer check, buffers: one chunk slot when the call's frames fit one chunk, else two
+int track_prepare(rship_ctx* c, const uint8_t* frames, uint32_t n_frames, const rship_track_cfg* cfg, TrackGeom* t) {
+    if (!frames || n_frames < 2) return set_err(c, "track: need at least 2 frames");
+    if (track_geom(c, cfg, t) || track_check_pointer(c, frames)) return 1;
+    const uint32_t slots = n_frames > t->chunk ? 2 : 1;
+    const uint32_t cnt = std::min(t->chunk, n_frames);
+    t->chunk = cnt; // (a slot never holds more than the call's frames)
+    for (uint32_t s = 0; s < slots; ++s)
+        if (ensure(c, c->trk_slot[s], (size_t)cnt * (t->u8_stride + 4 * t->pyr_stride))) return 1;
+    for (hipEvent_t* e : {&c->trk_up[0], &c->trk_up[1], &c->trk_k[0], &c->trk_k[1]})
+        if (!*e) RS_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
+    return 0;
+}
+
+} // namespace
+
+extern "C" {
+
+int rship_track_frames(rship_ctx* c, const uint8_t* frames, uint32_t n_frames, size_t pitch, size_t frame_stride,
+                       const rship_track_cfg* cfg, float* flow, uint8_t* status, float* residual) {
+    DeviceGuard dev_guard(c);
+    TrackGeom t;
+    if (track_prepare(c, frames, n_frames, cfg, &t)) return 1;
+    const uint32_t P = t.n_points, n_pairs = n_frames - 1;
+    if ((uint64_t)n_pairs * P >= (1ull << 31)) return set_err(c, "track: too many points in one call");
+    const size_t n_out = (size_t)n_pairs * P;
+    if (!n_out) return 0;
+    if (ensure(c, c->trk_out, n_out * 16)) return 1;
+    float2* d_flow = (float2*)c->trk_out.p;
+    float* d_res = (float*)(d_flow + n_out);
+    uint8_t* d_st = (uint8_t*)(d_res + n_out);
+    TrackArgs A{};
+    A.pyr_stride = t.pyr_stride;
+    A.u8_stride = t.u8_stride;
+    A.levels = cfg->levels;
+    A.n_points = P;
+    A.ny = t.ny;
+    A.step = cfg->step;
+    A.win = cfg->window;
+    A.max_iters = cfg->max_iters;
+    A.eps2 = cfg->epsilon * cfg->epsilon;
+    A.min_eig = cfg->min_eig;
+    A.L = t.L;
+    // chunk j holds frames [f0, f0 + cnt) and tracks pairs f0 .. f0 + cnt - 2; the next chunk starts at its last frame, so
+    // every pair lies in exactly one chunk and a pair's result does not depend on where the chunks are cut
+    bool used[2] = {false, false};
+    uint32_t f0 = 0;
+    int slot = 0;
+    if (track_upload(c, t, 0, false, frames, 0, std::min(t.chunk, n_frames), pitch, frame_stride)) return 1;
+    for (;;) {
+        const uint32_t cnt = std::min(t.chunk, n_frames - f0);
+        if (track_pyramid(c, t, slot, cnt, cfg->levels)) return 1;
+        A.u8 = (const uint8_t*)c->trk_slot[slot].p;
+        A.pyr = (const float*)(A.u8 + (size_t)t.chunk * t.u8_stride);
+        A.n_pairs = cnt - 1;
+        A.flow = d_flow + (size_t)f0 * P;
+        A.resid = d_res + (size_t)f0 * P;
+        A.status = d_st + (size_t)f0 * P;
+        const uint32_t waves = A.n_pairs * P;
+        hipLaunchKernelGGL(lk_kernel, dim3((waves + 3) / 4), dim3(256), 0, c->stream, A);
+        RS_HIP(hipGetLastError());
+        RS_HIP(hipEventRecord(c->trk_k[slot], c->stream));
+        used[slot] = true;
+        const uint32_t next = f0 + cnt - 1;
+        if (next >= n_frames - 1) break;
+        slot ^= 1;
+        if (track_upload(c, t, slot, used[slot], frames, next, std::min(t.chunk, n_frames - next), pitch, frame_stride)) return 1;
+        f0 = next;
+    }
+    RS_HIP(hipMemcpyAsync(flow, d_flow, n_out * 8, hipMemcpyDeviceToHost, c->stream));
+    RS_HIP(hipMemcpyAsync(residual, d_res, n_out * 4, hipMemcpyDeviceToHost, c->stream));
+    RS_HIP(hipMemcpyAsync(status, d_st, n_out, hipMemcpyDeviceToHost, c->stream));
+    return sync_stream(c);
+}
+
+int rship_track_pyramid(rship_ctx* c, const uint8_t* frames, uint32_t n_frames, size_t pitch, size_t frame_stride,
+                        const rship_track_cfg* cfg, float* out) {
+    DeviceGuard dev_guard(c);
+    TrackGeom t;
+    if (track_prepare(c, frames, n_frames, cfg, &t)) return 1;
+    if (n_frames > t.chunk) return set_err(c, "track_pyramid: the frames do not fit one chunk");
+    if (track_upload(c, t, 0, false, frames, 0, n_frames, pitch, frame_stride)) return 1;
+    if (track_pyramid(c, t, 0, n_frames, cfg->levels)) return 1;
+    const float* pyr = (const float*)((const uint8_t*)c->trk_slot[0].p + (size_t)t.chunk * t.u8_stride);
+    uint64_t per = 0;
+    for (uint32_t l = 1; l < cfg->levels; ++l) per += (uint64_t)t.L.w[l] * t.L.h[l];
+    if (per)
+        RS_HIP(hipMemcpy2DAsync(out, per * 4, pyr, t.pyr_stride * 4, per * 4, n_frames, hipMemcpyDeviceToHost, c->stream));
+    return sync_stream(c);
 }
 
 } // extern "C"

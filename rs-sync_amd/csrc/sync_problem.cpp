@@ -15,6 +15,7 @@
 #include "../../include/rssync.h"
 #include "../../include/rssync_c.h"
 #include "../../include/rssync_hip.h"
+#include "host_errors.hpp"
 #include "roctx_ranges.hpp"
 
 #include <algorithm>
@@ -34,16 +35,12 @@
 #include <thread>
 #include <vector>
 
-namespace {
-
 // ---------------------------------------------------------------------------
-// error convention: core_support/panic.cpp:7-15
+// error convention: core_support/panic.cpp:7-15 (declared in host_errors.hpp, shared with track_api.cpp)
 
-struct PanicError : std::runtime_error {
-    using std::runtime_error::runtime_error;
-};
+namespace rssync_host {
 
-int g_panic_mode = 0; // 0 = reference behaviour, 1 = throw (caught by the C-ABI)
+int g_panic_mode = 0;
 thread_local std::string g_last_error;
 
 [[noreturn]] void panic(const std::string& reason) {
@@ -55,6 +52,16 @@ thread_local std::string g_last_error;
     std::cerr << "rssync panic: " << reason << std::endl;
     std::exit(1);
 }
+
+} // namespace rssync_host
+
+using rssync_host::g_last_error;
+using rssync_host::g_panic_mode;
+using rssync_host::guarded;
+using rssync_host::panic;
+using rssync_host::PanicError;
+
+namespace {
 
 bool all_finite(const double* v, size_t n) {
     for (size_t i = 0; i < n; ++i)
@@ -1847,22 +1854,6 @@ struct rssync_problem {
     SyncProblemHip* impl;
     bool owns = true;
 };
-
-namespace {
-template <typename F>
-int guarded(F&& f) {
-    try {
-        f();
-        return 0;
-    } catch (const PanicError& e) {
-        g_last_error = e.what();
-        return 1;
-    } catch (const std::exception& e) {
-        g_last_error = std::string("exception: ") + e.what();
-        return 2;
-    }
-}
-} // namespace
 
 extern "C" {
 

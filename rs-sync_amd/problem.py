@@ -600,6 +600,20 @@ class SyncProblem:
         self._lib.rssync_ext_sync_trace(self._h, _p(t), cap, C.byref(n))
         return t[:min(n.value, cap)].copy()
 
+    def track_points(self, frames, grid_step=200, **params):
+        """Sparse pyramidal Lucas-Kanade at the driver's grid (include/rssync_track.h, rssync_amd.track): frames is an
+        (n, H, W) uint8 numpy array or a uint8 torch tensor on this problem's device ->
+        (points_a (P, 2), points_b (n-1, P, 2), status (n-1, P) uint8, residual (n-1, P) float32).  params: window,
+        levels, max_iters, epsilon, min_eig.  Nothing is stored in the problem."""
+        from . import track
+        return track.track_points(self, frames, grid_step=grid_step, **params)
+
+    def track_frames(self, frames, frame_times, lens, first_frame=0, grid_step=200, **params):
+        """track_points, then set_track_pixels(first_frame + k, frame_times[k], frame_times[k+1], grid, b_k, lens, H)
+        for every pair k (core_testcode.cpp:97-158).  A long video goes in overlapping batches: INTEGRATION.md."""
+        from . import track
+        track.track_frames(self, frames, frame_times, lens, first_frame=first_frame, grid_step=grid_step, **params)
+
     def device_context(self):
         """rship_ctx* of this problem (include/rssync_hip.h), for kernel-level tools."""
         return self._lib.rssync_ext_device_context(self._h)
