@@ -195,12 +195,44 @@ __device__ __forceinline__ float smin2_of(uint32_t n2min_bits) {
 // counter for 3 of every 8 registers, to take load off the scalar unit -- two scalar instructions per
 // register run at ~6 cycles per register per SIMD, tools/ubench/valu_rate.hip -- changed the kernel by
 // -1.5 % .. +0.5 % depending on the build: not kept.)
-template <int NR, int R0 = 0, int R1 = NR> // registers [R0, R1)
+// G = 4: the four compares of a group are issued back to back into four SGPR pairs, and only then counted.  hipcc
+// otherwise sends every v_cmp through the same pair, so each s_bcnt1 waits for the compare just before it and the next
+// compare for that s_bcnt1 -- one dependent VALU -> SALU round trip per register.  Same masks, same counts
+// (profiles/r7_k2_count_groups_ab.txt).  The four pairs cost SGPRs, and with them some instantiations spill: the tile
+// kernel uses the grouped form only where it does not (lmeds_kernel: CG).
+#ifndef RSSYNC_COUNT_GROUP   // (1: never grouped, for A/B builds)
+#define RSSYNC_COUNT_GROUP 4
+#endif
+template <int NR, int R0 = 0, int R1 = NR, int G = 1> // registers [R0, R1)
 __device__ __forceinline__ uint32_t wave_count_lt(const uint32_t (&r)[NR], uint32_t pivot) {
     const float pv = __uint_as_float(pivot);
     uint32_t cnt = 0;
+    int m = R0;
+#if RSSYNC_COUNT_GROUP == 4
+    if constexpr (G == 4) {
+        const uint32_t ps = (uint32_t)__builtin_amdgcn_readfirstlane((int)pivot);
 #pragma unroll
-    for (int m = R0; m < R1; ++m)
+        for (; m + 3 < R1; m += 4) {
+            // (the counts inside the same statement: left to itself, hipcc moves each s_bcnt1 back behind its compare)
+            uint64_t k0, k1, k2, k3;
+            uint32_t c0, c1, c2, c3;
+            asm("v_cmp_gt_f32_e64 %0, %8, |%9|\n\t"
+                "v_cmp_gt_f32_e64 %1, %8, |%10|\n\t"
+                "v_cmp_gt_f32_e64 %2, %8, |%11|\n\t"
+                "v_cmp_gt_f32_e64 %3, %8, |%12|\n\t"
+                "s_bcnt1_i32_b64 %4, %0\n\t"
+                "s_bcnt1_i32_b64 %5, %1\n\t"
+                "s_bcnt1_i32_b64 %6, %2\n\t"
+                "s_bcnt1_i32_b64 %7, %3"
+                : "=&s"(k0), "=&s"(k1), "=&s"(k2), "=&s"(k3), "=&s"(c0), "=&s"(c1), "=&s"(c2), "=&s"(c3)
+                : "s"(ps), "v"(r[m]), "v"(r[m + 1]), "v"(r[m + 2]), "v"(r[m + 3])
+                : "scc");
+            cnt += (c0 + c1) + (c2 + c3);
+        }
+    }
+#endif
+#pragma unroll
+    for (; m < R1; ++m)
         cnt += (uint32_t)__builtin_popcountll(__builtin_amdgcn_fcmpf(pv, fabsf(__uint_as_float(r[m])), 2 /* FCMP_OGT */));
     return cnt;
 }
@@ -252,7 +284,7 @@ __device__ __forceinline__ uint32_t uniform_u32(uint32_t v) { return (uint32_t)_
 struct Bracket {
     uint32_t lo, c_lo, hi, c_hi;
 };
-template <int NR>
+template <int NR, int G = 1> // G: wave_count_lt's grouping
 __device__ __forceinline__ void narrow_kth(const uint32_t (&r)[NR], uint32_t kq, Bracket& b, uint32_t stop_elems, uint32_t hi_limit) {
     uint32_t lo = b.lo, c_lo = b.c_lo, hi = b.hi, c_hi = b.c_hi;
     uint32_t a1 = lo, c1 = c_lo, a2 = hi, c2 = c_hi; // the two most recent (pivot, count) points
@@ -288,7 +320,7 @@ __device__ __forceinline__ void narrow_kth(const uint32_t (&r)[NR], uint32_t kq,
             }
         }
         if (!(piv > lo && piv < hi)) piv = lo + ((hi - lo) >> 1); // bit bisection: guaranteed finish
-        const uint32_t c = wave_count_lt(r, piv);
+        const uint32_t c = wave_count_lt<NR, 0, NR, G>(r, piv);
         K2_COUNT(4);
         a1 = a2; c1 = c2;
         a2 = piv; c2 = c;
@@ -298,10 +330,10 @@ __device__ __forceinline__ void narrow_kth(const uint32_t (&r)[NR], uint32_t kq,
     b.lo = lo; b.c_lo = c_lo; b.hi = hi; b.c_hi = c_hi;
 }
 // the exact kq-th smallest, given an exclusive upper bound hi with count(|r| < hi) = c_hi > kq
-template <int NR>
+template <int NR, int G = 1>
 __device__ __forceinline__ uint32_t select_kth(const uint32_t (&r)[NR], uint32_t kq, uint32_t hi, uint32_t c_hi) {
     Bracket b{0u, 0u, hi, c_hi};
-    narrow_kth(r, kq, b, 0u, 0u);
+    narrow_kth<NR, G>(r, kq, b, 0u, 0u);
     return b.lo;
 }
 
@@ -569,6 +601,8 @@ __global__ __launch_bounds__(BLOCK, BLOCK == 512 ? 2 : (R64 ? 1 : (RPT >= 16 ? (
     constexpr int kHyp = kHypBatch;
     constexpr int ROWS = BLOCK * RPT;
     constexpr int NR = ROWS / 64; // residual registers per lane: a wave spans the whole tile
+    // grouped counting (wave_count_lt) where it costs no spill: the benchmark's shape with the compiled-in window
+    constexpr int CG = (MODE == 0 && RPT == 8 && BLOCK == 256 && CAPW != 0 && !R64) ? 4 : 1;
     __shared__ __attribute__((aligned(16))) float s_n[3][ROWS];
     f4* s_win;
     if constexpr (CAPW != 0) {
@@ -777,7 +811,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK == 512 ? 2 : (R64 ? 1 : (RPT >= 16 ? (
                     const unsigned long long key = __hip_atomic_load(&s_key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                     const uint32_t T = (uint32_t)(key >> 32), g = (uint32_t)key;
                     uint32_t hi2 = T + ((T != kInfBits && g > h) ? 1u : 0u);
-                    const uint32_t tot = wave_count_lt(r2, hi2);
+                    const uint32_t tot = wave_count_lt<NR, 0, NR, CG>(r2, hi2);
                     if (tot > kq) {
                         K2_COUNT(3);
                         if (hi2 == kInfBits) { // no bound yet: start the bracket at the largest residual
@@ -788,7 +822,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK == 512 ? 2 : (R64 ? 1 : (RPT >= 16 ? (
                             mx = wave_max_f32(mx);
                             if (finite_f(mx)) hi2 = __float_as_uint(mx) + 1u; // count(|r| < hi2) is still tot
                         }
-                        const uint32_t kth = select_kth(r2, kq, hi2, tot);
+                        const uint32_t kth = select_kth<NR, CG>(r2, kq, hi2, tot);
                         if (lane == 0) atomicMin(&s_key, ((unsigned long long)kth << 32) | h);
                     }
                 }
@@ -835,14 +869,14 @@ __global__ __launch_bounds__(BLOCK, BLOCK == 512 ? 2 : (R64 ? 1 : (RPT >= 16 ? (
                         // not lift the count above kq, the last group of rows is neither read nor multiplied.
                         constexpr int GL = NR / 4 - 1;
                         sweep_tile<NR, 0, GL>(p4x, p4y, p4z, lane, f3{hv.x, hv.y, hv.z}, r2);
-                        tot = wave_count_lt<NR, 0, 4 * GL>(r2, T);
+                        tot = wave_count_lt<NR, 0, 4 * GL, CG>(r2, T);
                         if (tot + 256u <= kq) continue;
                         K2_COUNT(9);
                         sweep_tile<NR, GL, GL + 1>(p4x, p4y, p4z, lane, f3{hv.x, hv.y, hv.z}, r2);
-                        tot += wave_count_lt<NR, 4 * GL, NR>(r2, T);
+                        tot += wave_count_lt<NR, 4 * GL, NR, CG>(r2, T);
                     } else {
                         sweep_tile(p4x, p4y, p4z, lane, f3{hv.x, hv.y, hv.z}, r2);
-                        tot = wave_count_lt(r2, T);
+                        tot = wave_count_lt<NR, 0, NR, CG>(r2, T);
                     }
                     if (tot > kq) {
                         K2_COUNT(3);
@@ -855,7 +889,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK == 512 ? 2 : (R64 ? 1 : (RPT >= 16 ? (
                             mx = wave_max_f32(mx);
                             if (finite_f(mx)) b.hi = __float_as_uint(mx) + 1u; // count(|r| < hi) is still tot
                         }
-                        narrow_kth(r2, kq, b, kLazyElems, T); // until it ends below T and holds <= kLazyElems elements (or is closed)
+                        narrow_kth<NR, CG>(r2, kq, b, kLazyElems, T); // until it ends below T and holds <= kLazyElems elements (or is closed)
                         uint32_t slot = 0;
                         if (lane == 0) {
                             atomicMin(&s_key, (unsigned long long)b.hi << 32);
