@@ -13,3 +13,4 @@ from . import synth  # noqa: F401
 from . import dist  # noqa: F401
 from . import quality  # noqa: F401
 from . import track  # noqa: F401
+from . import features  # noqa: F401

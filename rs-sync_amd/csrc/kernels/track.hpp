@@ -13,7 +13,8 @@
 //                    21 x 21 window are 7 per lane -- and so does the 2 x 2 structure tensor; one iteration samples
 //                    frame k+1 bilinearly at the current position and reduces the two right-hand-side sums across the
 //                    wave with a shuffle butterfly, which leaves the identical sum in every lane: every lane solves the
-//                    2 x 2 system itself and the wave takes the same branch without a trip through LDS.
+//                    2 x 2 system itself and the wave takes the same branch without a trip through LDS.  The body is
+//                    lk_point, which kernels/features.hpp's lkfb_kernel calls too.
 //
 // Pixel arithmetic is relative to the integer base of the point (floor of the point at that level): positions are
 // int base + fp32 offset, so fp32 keeps sub-pixel resolution at x ~ 4000.  The kernel returns the FLOW; the host adds it
@@ -117,13 +118,19 @@ __device__ __forceinline__ float track_sample(const TrackArgs& A, uint32_t f, in
 // status codes (include/rssync_track.h)
 constexpr uint8_t kTrackOk = 0, kTrackIllConditioned = 1, kTrackLeftImage = 2, kTrackIterCap = 3;
 
-__global__ __launch_bounds__(256) void lk_kernel(TrackArgs A) {
-    const uint32_t g = blockIdx.x * 4 + threadIdx.x / 64; // one wave per (pair, point)
+// LK of one point from frame fa (the template) to frame fb of the chunk, started at the level-0 position (ax + fx0,
+// ay + fy0): an integer base plus a fraction in [0, 1).  FRAC = false is the integer start (fx0 = fy0 = 0 and never
+// read), the grid point of lk_kernel; FRAC = true carries the fraction into every level, the template included, so a
+// fraction of 0 gives the integer path's numbers.  RESID: also the mean |I_b - T| at the final position.  Returns the
+// flow (relative to the start) at level 0.
+struct LkOut {
+    float flx, fly, res;
+    uint8_t st;
+};
+
+template <bool FRAC, bool RESID>
+__device__ __forceinline__ LkOut lk_point(const TrackArgs& A, uint32_t fa, uint32_t fb, int ax, int ay, float fx0, float fy0) {
     const int lane = threadIdx.x & 63;
-    if (g >= A.n_pairs * A.n_points) return;
-    const uint32_t pair = g / A.n_points, pt = g - pair * A.n_points;
-    // the driver's grid (core_testcode.cpp:124-132): x-major, i = step, 2 step, ... < width
-    const int ax = (int)((pt / A.ny + 1) * A.step), ay = (int)((pt % A.ny + 1) * A.step);
     const int win = (int)A.win, r = win / 2, area = win * win;
     int dx[kTrackPerLane], dy[kTrackPerLane];
 #pragma unroll
@@ -140,7 +147,9 @@ __global__ __launch_bounds__(256) void lk_kernel(TrackArgs A) {
         if (l != (int)A.levels - 1) { flx *= 2.f; fly *= 2.f; }
         const int bx = ax >> l, by = ay >> l;                 // integer base of the point at this level
         const float sc = 1.0f / (float)(1 << l);
-        const float fax = (float)(ax - (bx << l)) * sc, fay = (float)(ay - (by << l)) * sc; // its fraction (exact)
+        // its fraction (exact for an integer start)
+        const float fax = FRAC ? ((float)(ax - (bx << l)) + fx0) * sc : (float)(ax - (bx << l)) * sc;
+        const float fay = FRAC ? ((float)(ay - (by << l)) + fy0) * sc : (float)(ay - (by << l)) * sc;
         const int w = (int)A.L.w[l], h = (int)A.L.h[l];
         float hxx = 0.f, hxy = 0.f, hyy = 0.f;
 #pragma unroll
@@ -148,9 +157,9 @@ __global__ __launch_bounds__(256) void lk_kernel(TrackArgs A) {
             T[j] = GX[j] = GY[j] = 0.f;
             if (!valid(j)) continue;
             const int x = bx + dx[j], y = by + dy[j];
-            T[j] = track_sample(A, pair, l, x, y, fax, fay);
-            GX[j] = 0.5f * (track_sample(A, pair, l, x + 1, y, fax, fay) - track_sample(A, pair, l, x - 1, y, fax, fay));
-            GY[j] = 0.5f * (track_sample(A, pair, l, x, y + 1, fax, fay) - track_sample(A, pair, l, x, y - 1, fax, fay));
+            T[j] = track_sample(A, fa, l, x, y, fax, fay);
+            GX[j] = 0.5f * (track_sample(A, fa, l, x + 1, y, fax, fay) - track_sample(A, fa, l, x - 1, y, fax, fay));
+            GY[j] = 0.5f * (track_sample(A, fa, l, x, y + 1, fax, fay) - track_sample(A, fa, l, x, y - 1, fax, fay));
             hxx += GX[j] * GX[j];
             hxy += GX[j] * GY[j];
             hyy += GY[j] * GY[j];
@@ -180,7 +189,7 @@ __global__ __launch_bounds__(256) void lk_kernel(TrackArgs A) {
 #pragma unroll
             for (int j = 0; j < kTrackPerLane; ++j) {
                 if (!valid(j)) continue;
-                const float e = track_sample(A, pair + 1, l, ix + dx[j], iy + dy[j], fx, fy) - T[j];
+                const float e = track_sample(A, fb, l, ix + dx[j], iy + dy[j], fx, fy) - T[j];
                 ex += GX[j] * e;
                 ey += GY[j] * e;
             }
@@ -195,24 +204,39 @@ __global__ __launch_bounds__(256) void lk_kernel(TrackArgs A) {
         if (!conv && l == 0) st = kTrackIterCap;
     }
     const int W = (int)A.L.w[0], H = (int)A.L.h[0];
-    if (st != kTrackLeftImage && (flx < (float)-ax || flx > (float)(W - 1 - ax) || fly < (float)-ay || fly > (float)(H - 1 - ay)))
+    const float ox = FRAC ? fx0 + flx : flx, oy = FRAC ? fy0 + fly : fly; // final position relative to (ax, ay)
+    if (st != kTrackLeftImage && (ox < (float)-ax || ox > (float)(W - 1 - ax) || oy < (float)-ay || oy > (float)(H - 1 - ay)))
         st = kTrackLeftImage;
-    // mean absolute residual at the final position, level 0 (template = frame k's pixels around the integer point)
-    const float cx = fminf(fmaxf(flx, (float)(-ax - 1)), (float)(W - ax)), cy = fminf(fmaxf(fly, (float)(-ay - 1)), (float)(H - ay));
-    const float ipx = floorf(cx), ipy = floorf(cy);
-    const int ix = ax + (int)ipx, iy = ay + (int)ipy;
-    const float fx = cx - ipx, fy = cy - ipy;
     float res = 0.f;
+    if (RESID) {
+        // mean absolute residual at the final position, level 0 (template = frame fa's pixels around the start point)
+        const float cx = fminf(fmaxf(ox, (float)(-ax - 1)), (float)(W - ax)), cy = fminf(fmaxf(oy, (float)(-ay - 1)), (float)(H - ay));
+        const float ipx = floorf(cx), ipy = floorf(cy);
+        const int ix = ax + (int)ipx, iy = ay + (int)ipy;
+        const float fx = cx - ipx, fy = cy - ipy;
 #pragma unroll
-    for (int j = 0; j < kTrackPerLane; ++j) {
-        if (!valid(j)) continue;
-        res += fabsf(track_sample(A, pair + 1, 0, ix + dx[j], iy + dy[j], fx, fy) - track_sample(A, pair, 0, ax + dx[j], ay + dy[j], 0.f, 0.f));
+        for (int j = 0; j < kTrackPerLane; ++j) {
+            if (!valid(j)) continue;
+            res += fabsf(track_sample(A, fb, 0, ix + dx[j], iy + dy[j], fx, fy) -
+                         track_sample(A, fa, 0, ax + dx[j], ay + dy[j], FRAC ? fx0 : 0.f, FRAC ? fy0 : 0.f));
+        }
+        res = wave_allsum(res) / (float)area;
     }
-    res = wave_allsum(res) / (float)area;
+    return LkOut{flx, fly, res, st};
+}
+
+__global__ __launch_bounds__(256) void lk_kernel(TrackArgs A) {
+    const uint32_t g = blockIdx.x * 4 + threadIdx.x / 64; // one wave per (pair, point)
+    const int lane = threadIdx.x & 63;
+    if (g >= A.n_pairs * A.n_points) return;
+    const uint32_t pair = g / A.n_points, pt = g - pair * A.n_points;
+    // the driver's grid (core_testcode.cpp:124-132): x-major, i = step, 2 step, ... < width
+    const int ax = (int)((pt / A.ny + 1) * A.step), ay = (int)((pt % A.ny + 1) * A.step);
+    const LkOut o = lk_point<false, true>(A, pair, pair + 1, ax, ay, 0.f, 0.f);
     if (lane == 0) {
-        A.flow[g] = make_float2(flx, fly);
-        A.status[g] = st;
-        A.resid[g] = res;
+        A.flow[g] = make_float2(o.flx, o.fly);
+        A.status[g] = o.st;
+        A.resid[g] = o.res;
     }
 }
 

@@ -20,6 +20,8 @@
 //                      table (kernels/gyro.hpp).
 //   pyr_down_kernel, lk_kernel  the tracker: image pyramid + sparse pyramidal Lucas-Kanade at the
 //                      driver's grid points (kernels/track.hpp).
+//   corner_*, lkfb_kernel  corner detection per cell and forward-backward LK of the detected corners
+//                      (kernels/features.hpp).
 // Data layout and the roofline that bounds each kernel: DESIGN.md.
 // The kernels live in kernels/*.hpp (one header each, included below); this file holds the
 // device context and the launchers.
@@ -66,6 +68,7 @@ using rs::f4;
 #include "kernels/executor.hpp"
 #include "kernels/gyro.hpp"
 #include "kernels/track.hpp"
+#include "kernels/features.hpp"
 
 // ===========================================================================
 // host side of the C-ABI
@@ -108,6 +111,8 @@ struct rship_ctx {
     uint32_t g_n = 0; // samples of the last rship_gyro_rates_upload
     // tracker (rship_track_*): two chunk slots (frames + pyramid), the outputs of one call; upload / kernel events per slot
     DevBuf trk_slot[2], trk_out;
+    // features (rship_features_track, rship_track_list): per-cell detector results of a chunk, the lists and outputs of a call
+    DevBuf ftr_cells, ftr_out;
     hipEvent_t trk_up[2] = {}, trk_k[2] = {};
     int64_t g_first_us = 0, g_last_us = 0;
     std::vector<hipStream_t> loop_streams; // rship_sync_run: one per group of windows
@@ -1078,7 +1083,7 @@ void rship_destroy(rship_ctx* c) {
                       &c->frame_cost, &c->best_h, &c->costs, &c->part, &c->flags, &c->stats, &c->redo_mask, &c->redo_delays, &c->redo_count, &c->init_delays64, &c->dump,
                       &c->big_scratch, &c->mo_scratch, &c->mo_evals, &c->mo_order,
                       &c->g_ts, &c->g_rates, &c->g_us, &c->g_dq, &c->g_q, &c->g_knots, &c->g_cf, &c->g_status,
-                      &c->trk_slot[0], &c->trk_slot[1], &c->trk_out};
+                      &c->trk_slot[0], &c->trk_slot[1], &c->trk_out, &c->ftr_cells, &c->ftr_out};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     if (c->pinned) (void)hipHostFree(c->pinned);
@@ -3087,7 +3092,7 @@ struct TrackGeom {
 };
 
 int track_geom(rship_ctx* c, const rship_track_cfg* g, TrackGeom* t) {
-    if (!g->width || !g->height || !g->step || g->levels < 1 || g->levels > (uint32_t)kTrackMaxLevels || g->window < 3 ||
+    if (!g->width || !g->height || g->levels < 1 || g->levels > (uint32_t)kTrackMaxLevels || g->window < 3 ||
         g->window > (uint32_t)kTrackMaxWin || !(g->window & 1))
         return set_err(c, "track: bad configuration");
     t->L = TrackLevels{};
@@ -3104,8 +3109,8 @@ int track_geom(rship_ctx* c, const rship_track_cfg* g, TrackGeom* t) {
     t->pyr_stride = (off + 63) / 64 * 64;
     const uint64_t per_frame = t->u8_stride + 4 * t->pyr_stride;
     t->chunk = (uint32_t)std::max<uint64_t>(2, std::min<uint64_t>(1u << 20, kTrackBudget / 2 / per_frame));
-    t->ny = (g->height - 1) / g->step;
-    t->n_points = ((g->width - 1) / g->step) * t->ny;
+    t->ny = g->step ? (g->height - 1) / g->step : 0; // (no grid: the feature tracker's lists)
+    t->n_points = g->step ? ((g->width - 1) / g->step) * t->ny : 0;
     return 0;
 }
 
@@ -3175,6 +3180,7 @@ extern "C" {
 int rship_track_frames(rship_ctx* c, const uint8_t* frames, uint32_t n_frames, size_t pitch, size_t frame_stride,
                        const rship_track_cfg* cfg, float* flow, uint8_t* status, float* residual) {
     DeviceGuard dev_guard(c);
+    if (!cfg->step) return set_err(c, "track: bad configuration");
     TrackGeom t;
     if (track_prepare(c, frames, n_frames, cfg, &t)) return 1;
     const uint32_t P = t.n_points, n_pairs = n_frames - 1;
@@ -3242,6 +3248,171 @@ int rship_track_pyramid(rship_ctx* c, const uint8_t* frames, uint32_t n_frames, 
     for (uint32_t l = 1; l < cfg->levels; ++l) per += (uint64_t)t.L.w[l] * t.L.h[l];
     if (per)
         RS_HIP(hipMemcpy2DAsync(out, per * 4, pyr, t.pyr_stride * 4, per * 4, n_frames, hipMemcpyDeviceToHost, c->stream));
+    return sync_stream(c);
+}
+
+} // extern "C"
+
+// ===========================================================================
+// corner features and tracking from a list (kernels/features.hpp; declared in track_hip.h, called by features_api.cpp)
+
+namespace {
+
+TrackArgs track_args(const TrackGeom& t, const rship_track_cfg* cfg) {
+    TrackArgs A{};
+    A.pyr_stride = t.pyr_stride;
+    A.u8_stride = t.u8_stride;
+    A.levels = cfg->levels;
+    A.win = cfg->window;
+    A.max_iters = cfg->max_iters;
+    A.eps2 = cfg->epsilon * cfg->epsilon;
+    A.min_eig = cfg->min_eig;
+    A.L = t.L;
+    return A;
+}
+
+// rship_track_frames' chunk loop: chunk j holds frames [f0, f0 + cnt) and its pairs f0 .. f0 + cnt - 2; the next chunk
+// starts at its last frame, so every pair lies in exactly one chunk.  per_chunk(slot, f0, cnt) enqueues the chunk's
+// kernels on the context's stream after its pyramid.
+template <class F>
+int track_chunks(rship_ctx* c, const TrackGeom& t, const rship_track_cfg* cfg, const uint8_t* frames, uint32_t n_frames, size_t pitch,
+                 size_t fstride, F&& per_chunk) {
+    bool used[2] = {false, false};
+    uint32_t f0 = 0;
+    int slot = 0;
+    if (track_upload(c, t, 0, false, frames, 0, std::min(t.chunk, n_frames), pitch, fstride)) return 1;
+    for (;;) {
+        const uint32_t cnt = std::min(t.chunk, n_frames - f0);
+        if (track_pyramid(c, t, slot, cnt, cfg->levels)) return 1;
+        if (per_chunk(slot, f0, cnt)) return 1;
+        RS_HIP(hipEventRecord(c->trk_k[slot], c->stream));
+        used[slot] = true;
+        const uint32_t next = f0 + cnt - 1;
+        if (next >= n_frames - 1) break;
+        slot ^= 1;
+        if (track_upload(c, t, slot, used[slot], frames, next, std::min(t.chunk, n_frames - next), pitch, fstride)) return 1;
+        f0 = next;
+    }
+    return 0;
+}
+
+} // namespace
+
+extern "C" {
+
+int rship_features_track(rship_ctx* c, const uint8_t* frames, uint32_t n_frames, size_t pitch, size_t frame_stride,
+                         const rship_feature_cfg* cfg, int32_t* points, uint32_t* counts, float* flow_fwd, float* flow_bwd,
+                         uint8_t* status, float* fb_error) {
+    DeviceGuard dev_guard(c);
+    const rship_track_cfg* lk = &cfg->lk;
+    if (cfg->cell < 16 || cfg->cell > (uint32_t)kCornerMaxCell || cfg->block < 3 || cfg->block > (uint32_t)kCornerMaxBlock ||
+        !(cfg->block & 1) || !(cfg->quality > 0.0 && cfg->quality <= 1.0) || !(cfg->max_fb_error >= 0.f))
+        return set_err(c, "features: bad configuration");
+    const uint32_t b = cfg->block / 2 + 1;
+    if (lk->width < 2 * b + 1 || lk->height < 2 * b + 1) return set_err(c, "features: frame too small for the block");
+    TrackGeom t;
+    if (track_prepare(c, frames, n_frames, lk, &t)) return 1;
+    const uint32_t W = lk->width, H = lk->height, cell = cfg->cell;
+    const uint32_t ncy = (H + cell - 1) / cell, S = ((W + cell - 1) / cell) * ncy, n_pairs = n_frames - 1;
+    if ((uint64_t)n_pairs * S >= (1ull << 31)) return set_err(c, "features: too many cells in one call");
+    const size_t n_out = (size_t)n_pairs * S;
+    // outputs of the call: lists (int2), forward and backward flow (float2), fb error, counts, status
+    if (ensure(c, c->ftr_out, n_out * 29 + (size_t)n_pairs * 4 + 64)) return 1;
+    if (ensure(c, c->ftr_cells, (size_t)t.chunk * S * 24)) return 1;
+    int2* d_pts = (int2*)c->ftr_out.p;
+    float2* d_ff = (float2*)(d_pts + n_out);
+    float2* d_fbk = d_ff + n_out;
+    float* d_fb = (float*)(d_fbk + n_out);
+    uint32_t* d_cnt = (uint32_t*)(d_fb + n_out);
+    uint8_t* d_st = (uint8_t*)(d_cnt + n_pairs);
+    int64_t* d_cmax = (int64_t*)c->ftr_cells.p;
+    int64_t* d_br = d_cmax + (size_t)t.chunk * S;
+    int64_t* d_bi = d_br + (size_t)t.chunk * S;
+    const int r = (int)cfg->block / 2, tp = (int)cell + 2 * (r + 2);
+    LkfbArgs L{};
+    L.T = track_args(t, lk);
+    L.slots = S;
+    L.max_fb = cfg->max_fb_error;
+    // detection covers the chunk's a-side frames f0 .. f0 + cnt - 2 only: a pair's result does not depend on the cuts
+    auto chunk = [&](int slot, uint32_t f0, uint32_t cnt) -> int {
+        const uint8_t* u8 = (const uint8_t*)c->trk_slot[slot].p;
+        const uint32_t na = cnt - 1;
+        CornerArgs A{u8, t.u8_stride, (int)W, (int)H, (int)cell, r, (int)ncy, (int)S, d_cmax, d_br, d_bi};
+        hipLaunchKernelGGL(corner_cell_kernel, dim3(na * S), dim3(kCornerThreads), (size_t)tp * tp, c->stream, A);
+        RS_HIP(hipGetLastError());
+        SelectArgs Q{d_cmax, d_br, d_bi, (int)W, (int)S, cfg->quality, d_pts + (size_t)f0 * S, d_cnt + f0};
+        hipLaunchKernelGGL(corner_select_kernel, dim3(na), dim3(kCornerThreads), 0, c->stream, Q);
+        RS_HIP(hipGetLastError());
+        L.T.u8 = u8;
+        L.T.pyr = (const float*)(u8 + (size_t)t.chunk * t.u8_stride);
+        L.T.n_pairs = na;
+        L.T.flow = d_ff + (size_t)f0 * S;
+        L.T.status = d_st + (size_t)f0 * S;
+        L.pts = d_pts + (size_t)f0 * S;
+        L.counts = d_cnt + f0;
+        L.flow_b = d_fbk + (size_t)f0 * S;
+        L.fb = d_fb + (size_t)f0 * S;
+        const uint32_t waves = na * S;
+        hipLaunchKernelGGL(lkfb_kernel<true>, dim3((waves + 3) / 4), dim3(256), 0, c->stream, L);
+        RS_HIP(hipGetLastError());
+        return 0;
+    };
+    if (track_chunks(c, t, lk, frames, n_frames, pitch, frame_stride, chunk)) return 1;
+    RS_HIP(hipMemcpyAsync(counts, d_cnt, (size_t)n_pairs * 4, hipMemcpyDeviceToHost, c->stream));
+    RS_HIP(hipMemcpyAsync(points, d_pts, n_out * 8, hipMemcpyDeviceToHost, c->stream));
+    RS_HIP(hipMemcpyAsync(flow_fwd, d_ff, n_out * 8, hipMemcpyDeviceToHost, c->stream));
+    RS_HIP(hipMemcpyAsync(flow_bwd, d_fbk, n_out * 8, hipMemcpyDeviceToHost, c->stream));
+    RS_HIP(hipMemcpyAsync(fb_error, d_fb, n_out * 4, hipMemcpyDeviceToHost, c->stream));
+    RS_HIP(hipMemcpyAsync(status, d_st, n_out, hipMemcpyDeviceToHost, c->stream));
+    return sync_stream(c);
+}
+
+int rship_track_list(rship_ctx* c, const uint8_t* frames, uint32_t n_frames, size_t pitch, size_t frame_stride,
+                     const rship_track_cfg* cfg, const int32_t* points, const uint32_t* counts, uint32_t cap, float* flow,
+                     uint8_t* status, float* residual) {
+    DeviceGuard dev_guard(c);
+    TrackGeom t;
+    if (track_prepare(c, frames, n_frames, cfg, &t)) return 1;
+    const uint32_t n_pairs = n_frames - 1;
+    if (!cap || (uint64_t)n_pairs * cap >= (1ull << 31)) return set_err(c, "track_list: bad list size");
+    for (uint32_t k = 0; k < n_pairs; ++k) {
+        if (counts[k] > cap) return set_err(c, "track_list: a count exceeds the list size");
+        for (uint32_t i = 0; i < counts[k]; ++i) {
+            const int32_t x = points[2 * ((size_t)k * cap + i)], y = points[2 * ((size_t)k * cap + i) + 1];
+            if (x < 0 || y < 0 || (uint32_t)x >= cfg->width || (uint32_t)y >= cfg->height) return set_err(c, "track_list: a point outside the frame");
+        }
+    }
+    const size_t n_out = (size_t)n_pairs * cap;
+    if (ensure(c, c->ftr_out, n_out * 21 + (size_t)n_pairs * 4 + 64)) return 1;
+    int2* d_pts = (int2*)c->ftr_out.p;
+    float2* d_flow = (float2*)(d_pts + n_out);
+    float* d_res = (float*)(d_flow + n_out);
+    uint32_t* d_cnt = (uint32_t*)(d_res + n_out);
+    uint8_t* d_st = (uint8_t*)(d_cnt + n_pairs);
+    RS_HIP(hipMemcpyAsync(d_pts, points, n_out * 8, hipMemcpyHostToDevice, c->stream));
+    RS_HIP(hipMemcpyAsync(d_cnt, counts, (size_t)n_pairs * 4, hipMemcpyHostToDevice, c->stream));
+    LkfbArgs L{};
+    L.T = track_args(t, cfg);
+    L.slots = cap;
+    auto chunk = [&](int slot, uint32_t f0, uint32_t cnt) -> int {
+        const uint8_t* u8 = (const uint8_t*)c->trk_slot[slot].p;
+        L.T.u8 = u8;
+        L.T.pyr = (const float*)(u8 + (size_t)t.chunk * t.u8_stride);
+        L.T.n_pairs = cnt - 1;
+        L.T.flow = d_flow + (size_t)f0 * cap;
+        L.T.status = d_st + (size_t)f0 * cap;
+        L.T.resid = d_res + (size_t)f0 * cap;
+        L.pts = d_pts + (size_t)f0 * cap;
+        L.counts = d_cnt + f0;
+        const uint32_t waves = (cnt - 1) * cap;
+        hipLaunchKernelGGL(lkfb_kernel<false>, dim3((waves + 3) / 4), dim3(256), 0, c->stream, L);
+        RS_HIP(hipGetLastError());
+        return 0;
+    };
+    if (track_chunks(c, t, cfg, frames, n_frames, pitch, frame_stride, chunk)) return 1;
+    RS_HIP(hipMemcpyAsync(flow, d_flow, n_out * 8, hipMemcpyDeviceToHost, c->stream));
+    RS_HIP(hipMemcpyAsync(residual, d_res, n_out * 4, hipMemcpyDeviceToHost, c->stream));
+    RS_HIP(hipMemcpyAsync(status, d_st, n_out, hipMemcpyDeviceToHost, c->stream));
     return sync_stream(c);
 }
 

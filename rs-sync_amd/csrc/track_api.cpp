@@ -15,9 +15,9 @@
 using rssync_host::guarded;
 using rssync_host::panic;
 
-namespace {
+namespace rssync_host {
 
-rship_track_cfg resolve(const rssync_track_params* p, size_t width, size_t height) {
+rship_track_cfg resolve_track_params(const rssync_track_params* p, size_t width, size_t height) {
     rssync_track_params q = p ? *p : rssync_track_params{};
     rship_track_cfg c{};
     if (q.grid_step < 0 || q.window < 0 || q.levels < 0 || q.max_iters < 0 || !(q.epsilon >= 0) || !(q.min_eig >= 0))
@@ -43,6 +43,12 @@ rship_track_cfg resolve(const rssync_track_params* p, size_t width, size_t heigh
     return c;
 }
 
+} // namespace rssync_host
+
+namespace {
+
+using rssync_host::resolve_track_params;
+
 struct Tracked {
     size_t n_points = 0;
     std::vector<float> flow;
@@ -61,7 +67,7 @@ Tracked track(rssync_problem* p, const uint8_t* frames, size_t n_frames, size_t 
     if (pitch < width) panic("track: pitch " + std::to_string(pitch) + " < width " + std::to_string(width));
     if (n_frames > 1 && frame_stride < pitch * height) panic("track: frame stride smaller than pitch * height");
     Tracked t;
-    t.cfg = resolve(params, width, height);
+    t.cfg = resolve_track_params(params, width, height);
     t.n_points = (size_t)((width - 1) / t.cfg.step) * ((height - 1) / t.cfg.step);
     const size_t n = (n_frames - 1) * t.n_points;
     t.flow.resize(2 * n);

@@ -39,7 +39,37 @@ int rship_track_frames(rship_ctx* c, const uint8_t* frames, uint32_t n_frames, s
 int rship_track_pyramid(rship_ctx* c, const uint8_t* frames, uint32_t n_frames, size_t pitch, size_t frame_stride,
                         const rship_track_cfg* cfg, float* out);
 
+/* corner features (features_api.cpp): every field resolved and checked there */
+typedef struct rship_feature_cfg {
+    rship_track_cfg lk;  /* step unused */
+    uint32_t cell;       /* 16 .. 128 */
+    uint32_t block;      /* odd, 3 .. 9 */
+    double quality;      /* (0, 1] */
+    float max_fb_error;  /* px */
+} rship_feature_cfg;
+
+/* Detect the corners of every frame but the last (kernels/features.hpp) and track each frame's list forward to the next
+ * frame and back.  S = ceil(w / cell) * ceil(h / cell) slots per pair: points[2 * (k * S + i)] (x, y), counts[k],
+ * flow_fwd / flow_bwd [2 * (k * S + i)], status[k * S + i] (0 .. 4), fb_error[k * S + i] (host buffers); entries at
+ * i >= counts[k] are unspecified.  Chunks, uploads and input kinds as rship_track_frames. */
+int rship_features_track(rship_ctx* c, const uint8_t* frames, uint32_t n_frames, size_t pitch, size_t frame_stride,
+                         const rship_feature_cfg* cfg, int32_t* points, uint32_t* counts, float* flow_fwd, float* flow_bwd,
+                         uint8_t* status, float* fb_error);
+/* for tests: LK of caller-given integer points, the forward pass of rship_features_track with the residual --
+ * lk_kernel's computation at points[2 * (k * cap + i)] for i < counts[k] (points inside the frame).  Outputs laid out as
+ * the points; cfg->step unused. */
+int rship_track_list(rship_ctx* c, const uint8_t* frames, uint32_t n_frames, size_t pitch, size_t frame_stride,
+                     const rship_track_cfg* cfg, const int32_t* points, const uint32_t* counts, uint32_t cap, float* flow,
+                     uint8_t* status, float* residual);
+
 #ifdef __cplusplus
 }
+
+struct rssync_track_params; // include/rssync_track.h
+
+namespace rssync_host __attribute__((visibility("hidden"))) {
+/* the tracker's parameters with their defaults resolved and checked (track_api.cpp; panics on a bad one) */
+rship_track_cfg resolve_track_params(const rssync_track_params* p, size_t width, size_t height);
+} // namespace rssync_host
 #endif
 #endif

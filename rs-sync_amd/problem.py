@@ -614,6 +614,20 @@ class SyncProblem:
         from . import track
         track.track_frames(self, frames, frame_times, lens, first_frame=first_frame, grid_step=grid_step, **params)
 
+    def track_features(self, frames, **params):
+        """Corner features per cell, tracked forward and backward (include/rssync_features.h, rssync_amd.features):
+        frames as in track_points -> Features(counts, points_a, points_b, status, fb_error), one row per pair whose
+        first counts[k] entries are set.  params: cell, block, quality, max_fb_error and the LK settings of
+        track_points.  Nothing is stored in the problem."""
+        from . import features
+        return features.track_features(self, frames, **params)
+
+    def features_frames(self, frames, frame_times, lens, first_frame=0, **params):
+        """track_features, then set_track_pixels(first_frame + k, frame_times[k], frame_times[k+1], a_k, b_k, lens, H)
+        with the status-0 tracks of every pair keeping at least min_tracks (default 8) -> the pairs handed on."""
+        from . import features
+        return features.features_frames(self, frames, frame_times, lens, first_frame=first_frame, **params)
+
     def device_context(self):
         """rship_ctx* of this problem (include/rssync_hip.h), for kernel-level tools."""
         return self._lib.rssync_ext_device_context(self._h)

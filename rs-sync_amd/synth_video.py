@@ -17,6 +17,8 @@ from . import synth
 BOX = 6.0               # half side of the box (m); the camera starts at its centre
 N_WAVES = 24
 WAVELENGTH = (0.35, 2.5)  # m: >= ~8 px at the far corners under grazing view, half-resolution lens
+FLAT_GRAY = 128           # render(flat=...): the flat region's value
+FLAT_EDGE = 0.5           # m: the width of the band outside the flat region over which the texture fades in
 
 
 def half_lens(lens=synth.LENS):
@@ -52,27 +54,46 @@ def _hit(c, d):
     return c + t * d
 
 
-def _shade(P, tex):
+def _shade(P, tex, weight=None):
+    """weight (render's flat=): the texture's share, 0 = FLAT_GRAY"""
     k, ph, amp = tex
     s = np.sin(P.astype(np.float32) @ k.T + ph) @ amp
     v = 128.0 + 100.0 * s / np.sqrt(0.5 * (amp ** 2).sum()) / 2.0
+    if weight is not None:
+        v = np.where(weight < 1, FLAT_GRAY + weight * (v - FLAT_GRAY), v)
     return np.clip(np.rint(v), 0, 255).astype(np.uint8)
 
 
 def render(gyro, frame_begin, frame_end, lens=synth.LENS, rows=synth.IMAGE_ROWS, cols=synth.IMAGE_COLS, seed=0,
-           d_true=synth.D_TRUE):
-    """-> frames (n, rows, cols) uint8, frame_times (n,) s, for frames [frame_begin, frame_end)"""
+           d_true=synth.D_TRUE, flat=None):
+    """-> frames (n, rows, cols) uint8, frame_times (n,) s, for frames [frame_begin, frame_end).
+
+    flat: None, or a world-space box ((x0, y0, z0), (x1, y1, z1)) whose part of the walls is rendered as constant gray
+    FLAT_GRAY (sky, a blank wall), the texture fading in over FLAT_EDGE m around it.  Then a third result,
+    mask (n, rows, cols) bool: the pixels that see the region."""
     ys, xs = np.mgrid[0:rows, 0:cols]
     rays = synth.unproject(np.stack([xs, ys], axis=-1).astype(np.float64), lens)   # (rows, cols, 3), once per lens
     tex = _texture(seed)
     ro = lens[0]
     n = frame_end - frame_begin
     out = np.empty((n, rows, cols), np.uint8)
+    mask = np.zeros((n, rows, cols), bool) if flat is not None else None
     times = np.arange(frame_begin, frame_end) / synth.FPS
     for i, fr in enumerate(range(frame_begin, frame_end)):
         q = gyro.orientation(times[i] + ro * np.arange(rows) / rows + d_true)            # one orientation per row
         world = synth.rotate_inv(q[:, None, :], rays)
-        out[i] = _shade(_hit(camera_position(fr, seed), world), tex)
+        P = _hit(camera_position(fr, seed), world)
+        if flat is None:
+            out[i] = _shade(P, tex)
+        else:
+            # distance of the wall point to the region: 0 inside (flat), the texture fades in over FLAT_EDGE outside it
+            # -- a band-limited border like the texture's own, not an aliased step
+            lo, hi = np.asarray(flat[0], np.float64), np.asarray(flat[1], np.float64)
+            d = np.linalg.norm(np.maximum(np.maximum(lo - P, P - hi), 0.0), axis=-1)
+            mask[i] = d == 0.0
+            out[i] = _shade(P, tex, np.minimum(d / FLAT_EDGE, 1.0).astype(np.float32))
+    if flat is not None:
+        return out, times, mask
     return out, times
 
 
