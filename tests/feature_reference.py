@@ -82,22 +82,43 @@ def detect(frame, cell=64, block=5, quality=0.01):
     return np.stack([xs[keep], ys[keep]], axis=-1).astype(np.int64).reshape(-1, 2)
 
 
-def track_fb(pyr_a, pyr_b, pts, max_fb_error=0.5, **lk):
+def track_fb(pyr_a, pyr_b, pts, max_fb_error=0.5, diag=False, **lk):
     """-> flow_fwd (P, 2), flow_bwd (P, 2), status (P,), fb_error (P,) for the features pts of frame a.  The backward pass
-    runs from b = a + flow_fwd for the tracks of forward status 0; the others have a NaN fb_error."""
+    runs from b = a + flow_fwd for the tracks of forward status 0; the others have a NaN fb_error.  diag=True adds the
+    decision margins of tests/track_reference.py's track_pair, the smaller of the forward and the backward pass's."""
     pts = np.asarray(pts, np.float64).reshape(-1, 2)
-    flow, st, _ = tr.track_pair(pyr_a, pyr_b, pts, **lk)
+    if diag:
+        flow, st, _, m = tr.track_pair(pyr_a, pyr_b, pts, diag=True, **lk)
+    else:
+        flow, st, _ = tr.track_pair(pyr_a, pyr_b, pts, **lk)
     back = np.zeros_like(flow)
     fb = np.full(len(pts), np.nan)
     ok = st == tr.STATUS_OK
     if ok.any():
-        fb_flow, fb_st, _ = tr.track_pair(pyr_b, pyr_a, pts[ok] + flow[ok], **lk)
+        if diag:
+            fb_flow, fb_st, _, mb = tr.track_pair(pyr_b, pyr_a, pts[ok] + flow[ok], diag=True, **lk)
+            for k in ("eig", "det", "conv", "border"):
+                m[k][ok] = np.minimum(m[k][ok], mb[k])
+        else:
+            fb_flow, fb_st, _ = tr.track_pair(pyr_b, pyr_a, pts[ok] + flow[ok], **lk)
         back[ok] = fb_flow
         fb[ok] = np.linalg.norm(flow[ok] + fb_flow, axis=-1)
         bad = (fb_st != tr.STATUS_OK) | (fb[ok] > max_fb_error)
         st = st.copy()
         st[np.nonzero(ok)[0][bad]] = STATUS_FB_MISMATCH
+    if diag:
+        return flow, back, st, fb, m
     return flow, back, st, fb
+
+
+def fb_edge(fb_ref, max_fb=0.5, tol=1e-3):
+    """(P,) bool: the tracks whose reference fb error is within tol px of the bound, where fp32 and fp64 may split"""
+    return np.abs(np.nan_to_num(fb_ref, nan=1e9) - max_fb) < tol
+
+
+def fb_ok(st_dev, st_ref, fb_ref, max_fb=0.5, tol=1e-3):
+    """statuses equal, apart from tracks whose fb error is within tol px of the bound (fp32 against fp64)"""
+    return (st_dev == st_ref) | fb_edge(fb_ref, max_fb, tol)
 
 
 def track(frames, cell=64, block=5, quality=0.01, max_fb_error=0.5, levels=4, **lk):

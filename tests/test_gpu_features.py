@@ -83,10 +83,7 @@ def test_list_lk_equals_grid_lk(built, video):
     np.testing.assert_array_equal(lres, res)
 
 
-def _fb_ok(st_dev, st_ref, fb_ref, max_fb=0.5):
-    """statuses equal, apart from tracks whose fb error is within 1e-3 px of the bound (fp32 against fp64)"""
-    edge = np.abs(np.nan_to_num(fb_ref, nan=1e9) - max_fb) < 1e-3
-    return (st_dev == st_ref) | edge
+_fb_ok = fr.fb_ok
 
 
 def test_against_the_reference(built, video):

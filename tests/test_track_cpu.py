@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import track_reference as tr
+from track_scenes import shifted_pair as _shifted_pair
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "rs-sync_amd", "librssync_core.so")
@@ -97,21 +98,6 @@ def test_grid_is_the_drivers_loop(w, h, step):
         assert len(want) == 130                                 # the bench's reference driver workload
 
 
-def _texture(x, y, lo, hi, seed=5):
-    """band-limited pattern evaluated exactly at any position: 16 sinusoids, wavelengths lo .. hi px, every direction"""
-    rng = np.random.default_rng(seed)
-    v = np.zeros(np.broadcast(x, y).shape)
-    for _ in range(16):
-        lam, th, ph = rng.uniform(lo, hi), rng.uniform(0, np.pi), rng.uniform(0, 2 * np.pi)
-        v += np.sin(2 * np.pi / lam * (np.cos(th) * x + np.sin(th) * y) + ph)
-    return np.clip(np.rint(128 + 30 * v), 0, 255).astype(np.uint8)
-
-
-def _shifted_pair(sx, sy, lo, hi, w=420, h=340):
-    ys, xs = np.mgrid[0:h, 0:w].astype(np.float64)
-    return np.stack([_texture(xs, ys, lo, hi), _texture(xs - sx, ys - sy, lo, hi)])   # content moves by (+sx, +sy)
-
-
 def test_reference_recovers_integer_shifts():
     for sx, sy in ((7, -4), (-23, 11), (0, 0)):
         pa, pb, st, _ = tr.track(_shifted_pair(sx, sy, 16, 64), step=70)
@@ -158,3 +144,65 @@ def test_reference_on_the_rendered_video():
     assert ok.mean() >= 0.95, np.bincount(st.ravel())
     assert np.median(err[ok]) < RENDER_MEDIAN_PX and err[ok].max() < RENDER_MAX_PX, (np.median(err[ok]), err[ok].max())
     assert np.isfinite(res).all()
+
+
+def test_diagnostics_leave_the_results_unchanged():
+    pair = _shifted_pair(3.3, -1.6, 12, 60, w=200, h=160)
+    pyrs = [tr.pyramid(f, 3) for f in pair]
+    pts = tr.grid(200, 160, 30)
+    kw = dict(window=9, max_iters=5, epsilon=0.05, min_eig=2.0)
+    plain = tr.track_pair(pyrs[0], pyrs[1], pts, **kw)
+    flow, st, res, m = tr.track_pair(pyrs[0], pyrs[1], pts, diag=True, **kw)
+    for a, b in zip(plain, (flow, st, res)):
+        np.testing.assert_array_equal(a, b)
+    assert set(m) == {"eig", "det", "conv", "border", "left_level"}
+    assert all(v.shape == (len(pts),) for v in m.values())
+
+
+def test_a_point_on_the_min_eig_bound_is_near_a_decision():
+    """min_eig set to a point's own level-0 eigenvalue: that point's test is decided by rounding (fp64 passes it, the
+    kernel's fp32 may not), so it is excused; min_eig a hair above makes it ill-conditioned and is excused as well"""
+    pair = _shifted_pair(0.3, 0.2, 12, 60, w=120, h=120)
+    pyrs = [tr.pyramid(f, 2) for f in pair]
+    pts = np.array([[60.0, 60.0], [40.0, 70.0]])
+    me = tr.min_eigenvalue(pair[0], pts)
+    assert me[0] > 1.0                                       # textured: far from the default bound
+    for bound, want in ((me[0], tr.STATUS_OK), (me[0] * (1 + 1e-9), tr.STATUS_ILL)):
+        _, st, _, m = tr.track_pair(pyrs[0], pyrs[1], pts[:1], min_eig=bound, diag=True)
+        assert st[0] == want
+        assert m["eig"][0] < 1e-8 and tr.near_decision(m, 0.01)[0]
+
+
+def test_a_plain_interior_point_is_not_near_a_decision():
+    pair = _shifted_pair(0.3, 0.2, 12, 60, w=120, h=120)
+    pyrs = [tr.pyramid(f, 2) for f in pair]
+    flow, st, _, m = tr.track_pair(pyrs[0], pyrs[1], np.array([[60.0, 60.0]]), diag=True)
+    assert st[0] == tr.STATUS_OK and not tr.near_decision(m, 0.01)[0], m
+    assert m["border"][0] > 20 and m["eig"][0] > 1e-2 and m["det"][0] > 1e-2 and m["left_level"][0] == -1
+    assert np.isfinite(m["conv"][0])                         # it took convergence tests: it has a margin
+
+
+def test_border_margins_count_moved_positions_only():
+    """identical frames: the flow stays exactly 0, so a point on column width-1 sits exactly on the border line in fp32
+    as in fp64 -- no split is possible and nothing is excused.  Moved by a sub-pixel shift, the same point's border tests
+    have a margin: its distance to the line."""
+    pair = _shifted_pair(-0.3, 0.0, 12, 60, w=64, h=48)
+    pyr = tr.pyramid(pair[0], 1)
+    pts = np.array([[63.0, 20.0], [30.0, 20.0]])
+    flow, st, _, m = tr.track_pair(pyr, pyr, pts, diag=True)
+    assert (st == tr.STATUS_OK).all() and (flow == 0).all()
+    assert np.isinf(m["border"]).all() and not tr.near_decision(m, 0.01).any()
+    flow, st, _, m = tr.track_pair(pyr, tr.pyramid(pair[1], 1), pts, diag=True)
+    assert st[0] == tr.STATUS_OK and 0 < m["border"][0] <= abs(flow[0, 0]) + 1e-12, (flow[0], m["border"][0])
+    assert 19 < m["border"][1] < 21 and not tr.near_decision(m, 0.01)[1]
+
+
+def test_a_point_carried_out_at_a_coarse_level_records_that_level():
+    """a 40 px shift at level 3 of a 160 px wide frame: the points near the right edge leave there"""
+    pair = _shifted_pair(40.0, 0.0, 16, 64, w=160, h=96)
+    pyrs = [tr.pyramid(f, 4) for f in pair]
+    pts = tr.grid(160, 96, 16)
+    _, st, _, m = tr.track_pair(pyrs[0], pyrs[1], pts, diag=True)
+    coarse = m["left_level"] > 0
+    assert coarse.any() and (st[coarse] == tr.STATUS_LEFT).all()
+    assert (m["left_level"][st != tr.STATUS_LEFT] == -1).all()
