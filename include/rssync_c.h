@@ -251,6 +251,20 @@ int rssync_ext_orientation_sweep(rssync_problem* p, const double* timestamps_s, 
                                  const char* const* orientations, int n_orientations, double initial_delay,
                                  int64_t frame_begin, int64_t frame_end, double search_step, double search_radius,
                                  double* costs, double* delays);
+/* The readout sweep: the sensor's readout time (lens.ro) is often unknown, and a wrong one does not make the solver fail --
+ * it moves the delay by about half the error.  For each readouts[i] (seconds): every frame of [frame_begin, frame_end) as
+ * if set again by rssync_ext_set_track_pixels with lens.ro = readouts[i], then PreSync(initial_delay, frame_begin,
+ * frame_end, search_step, search_radius) -> costs[i], delays[i] (bit for bit that loop; the lowest cost marks the readout
+ * that fits).  The frames keep their own readout afterwards.  One pipeline on the device: the frames are re-timed between
+ * the sweeps (the ray directions do not depend on the readout), one wait, one exchange between ranks.
+ * Errors: a frame of the range set by rssync_set_track_result (it has no pixel rows), a non-finite or negative
+ * readout, n < 1. */
+int rssync_ext_readout_sweep(rssync_problem* p, const double* readouts, int n, double initial_delay,
+                             int64_t frame_begin, int64_t frame_end, double search_step, double search_radius,
+                             double* costs, double* delays);
+/* Give every pixel frame the readout ro (finite, >= 0), exactly as setting it again with lens.ro = ro would; frames set
+ * by rssync_set_track_result are not touched. */
+int rssync_ext_set_readout(rssync_problem* p, double ro);
 /* the packed device ray streams of one frame ({ax,bx,ay,by} and {az,bz,ta,tb} per pair), for tests */
 int rssync_ext_frame_rays(rssync_problem* p, int64_t frame, float* a4, float* b4, size_t cap, size_t* n);
 

@@ -71,7 +71,8 @@ typedef struct rship_frame {
 #define RSHIP_K_PIXELS 5 /* packing kernels: raw records (rays or pixels) -> packed fp32 + fp64 streams */
 #define RSHIP_K_GYRO 6   /* gyro pipeline: integration scan, resampling, spline solve */
 #define RSHIP_K_LOSS_GRAD 7 /* residual + robust loss + analytic d/d-delay (one delay per window) */
-#define RSHIP_K_COUNT 8
+#define RSHIP_K_RETIME 8 /* re-timing kernel: a new readout for the pixel frames (rship_retime_pixels) */
+#define RSHIP_K_COUNT 9
 
 int rship_create(rship_ctx** out, int device /* -1 = current device */);
 void rship_destroy(rship_ctx* c);
@@ -171,6 +172,16 @@ typedef struct rship_pack_frame {
  * reference checks the rays it is handed, core_private.cpp:199-200). */
 int rship_pack_frames(rship_ctx* c, const rship_frame* table, const rship_pack_frame* pack, uint32_t n_frames,
                       uint64_t total_rays, double start, double fs, uint32_t* bad);
+
+/* A new readout for the PIXEL frames without repacking them (the readout sweep, rssync_c.h: rssync_ext_readout_sweep).
+ * table = the frame table of the frames of the last rship_pack_frames (same order, track counts and ray offsets) as the
+ * host computes it for the new row times; ro[i] = the readout (s) of frame i (ignored for frames set as rays).  The table
+ * and the readouts are copied to the device and the re-timing kernel rewrites ta / tb of the packed streams (fp32 and
+ * fp64) from the pixel rows of the raw records -- the bits rship_pack_frames gives with those readouts; the ray directions
+ * stay.  What the spline windows are planned from follows the new table.  Asynchronous and in stream order (the caller's
+ * arrays may be reused at once); the selection, size classes and plan of the sums are left as they are, so that a batch of
+ * sweeps can re-time between two of its sweeps.  Several devices: call rship_set_problem_frames again afterwards. */
+int rship_retime_pixels(rship_ctx* c, const rship_frame* table, const double* ro, uint32_t n_frames);
 
 /* One object over several devices (optional): the frame-table records of ALL frames of the problem (only n_rays, tmin,
  * tmax, range_a, range_b are read), so that every shard plans its LDS spline windows from the same frames as a single

@@ -14,3 +14,4 @@ from . import dist  # noqa: F401
 from . import quality  # noqa: F401
 from . import track  # noqa: F401
 from . import features  # noqa: F401
+from . import readout  # noqa: F401

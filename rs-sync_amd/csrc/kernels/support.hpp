@@ -1,4 +1,4 @@
-// support.hpp -- segment sums, packing kernels (raw records -> packed streams), debug kernels
+// support.hpp -- segment sums, packing kernels (raw records -> packed streams), the re-timing kernel, debug kernels
 // Part of the single HIP translation unit rssync_kernels.hip (included there, in order).
 #pragma once
 
@@ -107,11 +107,19 @@ struct PackParams {
     uint32_t* bad;
 };
 
+// spline parameter of a pixel's row time relative to the frame's base knot: row_time (core_testcode.cpp:144-145), then
+// knot_offset (core_private.cpp:19-20 without the delay).  pack_frames_kernel and retime_pixels_kernel both take a pixel
+// frame's ta / tb from here, so that re-timing gives the bits a full repack with the same readout would.
+__device__ __forceinline__ double pixel_knot_offset(double ro, double py, double frame_time, double rows, double start, double fs,
+                                                   double base) {
+    return rs::knot_offset(rs::row_time(ro, py, frame_time, rows), start, fs, base);
+}
+
 __global__ __launch_bounds__(kBlock) void pack_frames_kernel(PackParams p) {
     const rship_pack_frame& fr = p.frames[blockIdx.x];
     const uint32_t n = fr.n_rays;
     for (uint32_t row = blockIdx.y * kBlock + threadIdx.x; row < n; row += gridDim.y * kBlock) {
-        double ra[3], rb[3], tsa, tsb;
+        double ra[3], rb[3], tsa, tsb, ta, tb;
         const double* rec = p.raw + fr.raw_offset;
         if (fr.is_pixels) {
             const double2* src = (const double2*)(rec + 4 * (size_t)row);
@@ -119,6 +127,8 @@ __global__ __launch_bounds__(kBlock) void pack_frames_kernel(PackParams p) {
             const rs::Lens lens{fr.lens[0], fr.lens[1], fr.lens[2], fr.lens[3], fr.lens[4], fr.lens[5], fr.lens[6], fr.lens[7], fr.lens[8]};
             rs::pixel_to_ray(lens, a.x, a.y, fr.time_a, fr.rows, ra, &tsa);
             rs::pixel_to_ray(lens, b.x, b.y, fr.time_b, fr.rows, rb, &tsb);
+            ta = pixel_knot_offset(lens.ro, a.y, fr.time_a, fr.rows, p.start, p.fs, fr.base);
+            tb = pixel_knot_offset(lens.ro, b.y, fr.time_b, fr.rows, p.start, p.fs, fr.base);
         } else {
             tsa = rec[row];
             tsb = rec[(size_t)n + row];
@@ -126,9 +136,9 @@ __global__ __launch_bounds__(kBlock) void pack_frames_kernel(PackParams p) {
             const double* pb = rec + 5 * (size_t)n + 3 * (size_t)row;
             ra[0] = pa[0]; ra[1] = pa[1]; ra[2] = pa[2];
             rb[0] = pb[0]; rb[1] = pb[1]; rb[2] = pb[2];
+            ta = rs::knot_offset(tsa, p.start, p.fs, fr.base);
+            tb = rs::knot_offset(tsb, p.start, p.fs, fr.base);
         }
-        const double ta = rs::knot_offset(tsa, p.start, p.fs, fr.base);
-        const double tb = rs::knot_offset(tsb, p.start, p.fs, fr.base);
         f4 o0, o1;
         o0.x = (float)ra[0]; o0.y = (float)rb[0]; o0.z = (float)ra[1]; o0.w = (float)rb[1];
         o1.x = (float)ra[2]; o1.y = (float)rb[2]; o1.z = (float)ta; o1.w = (float)tb;
@@ -141,6 +151,37 @@ __global__ __launch_bounds__(kBlock) void pack_frames_kernel(PackParams p) {
         p.q0[o] = double2{ra[0], rb[0]};
         p.q1[o] = double2{ra[1], rb[1]};
         p.q2[o] = double2{ra[2], rb[2]};
+        p.q3[o] = double2{ta, tb};
+    }
+}
+
+// Re-timing kernel: a new readout for the pixel frames without repacking them.  The ray directions do not depend on the
+// readout (core_testcode.cpp:147-152); only the row times do (:144-145).  Per pair it reads the two pixel rows y_a, y_b of
+// the raw record and rewrites the time parts of the packed streams -- rays_b[o].z / .w (fp32 ta, tb) and q3[o] (fp64
+// {ta, tb}) -- with pixel_knot_offset against the base knot of the frame table the launcher has just installed.  One
+// thread per pair, as pack_frames_kernel; 16 B read and 24 B written per pair.  Frames set as rays leave at once.
+struct RetimeParams {
+    const double* raw;
+    const rship_pack_frame* pack; // the records of the last rship_pack_frames (raw offset, times, rows)
+    const FrameRec* frames;       // the new frame table (base_knot)
+    const double* ro;             // [n_frames] readout of each frame
+    f4* rays_b;
+    double2* q3;
+    double start, fs;
+};
+
+__global__ __launch_bounds__(kBlock) void retime_pixels_kernel(RetimeParams p) {
+    const rship_pack_frame& fr = p.pack[blockIdx.x];
+    if (!fr.is_pixels) return;
+    const uint32_t n = fr.n_rays;
+    const double ro = p.ro[blockIdx.x], base = (double)p.frames[blockIdx.x].base_knot;
+    const double* rec = p.raw + fr.raw_offset;
+    for (uint32_t row = blockIdx.y * kBlock + threadIdx.x; row < n; row += gridDim.y * kBlock) {
+        const double ya = rec[4 * (size_t)row + 1], yb = rec[4 * (size_t)row + 3];
+        const double ta = pixel_knot_offset(ro, ya, fr.time_a, fr.rows, p.start, p.fs, base);
+        const double tb = pixel_knot_offset(ro, yb, fr.time_b, fr.rows, p.start, p.fs, base);
+        const size_t o = (size_t)fr.ray_offset + row;
+        ((float2*)(p.rays_b + o))[1] = make_float2((float)ta, (float)tb); // (.x / .y, the z components, stay)
         p.q3[o] = double2{ta, tb};
     }
 }

@@ -63,6 +63,16 @@ RS_LHD void undistort_point(const Lens& lens, double px, double py, double* ux, 
     *uy = yn * gain;
 }
 
+// absolute capture time of a point on image row py (:144-145): the frame's time plus the readout's share of the rows
+// above it.  The one expression of it: the packing kernel, the re-timing kernel (a new readout, rays unchanged) and the
+// CPU test double all evaluate this text, so that a re-timed stream has the bits of a repacked one.
+RS_LHD double row_time(double ro, double py, double frame_time_s, double image_rows) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    return frame_time_s + ro * (py / image_rows);
+}
+
 // one end of a track: pixel -> unit ray (:147-152) and absolute row time (:144-145)
 RS_LHD void pixel_to_ray(const Lens& lens, double px, double py, double frame_time_s, double image_rows,
                          double* ray, double* ts) {
@@ -76,7 +86,7 @@ RS_LHD void pixel_to_ray(const Lens& lens, double px, double py, double frame_ti
     ray[0] = ux / inv;
     ray[1] = uy / inv;
     ray[2] = 1. / inv;
-    *ts = frame_time_s + lens.ro * (py / image_rows);
+    *ts = row_time(lens.ro, py, frame_time_s, image_rows);
 }
 
 // spline parameter of a row time relative to the frame's integer base knot

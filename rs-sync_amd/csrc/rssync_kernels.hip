@@ -98,6 +98,13 @@ struct rship_ctx {
     std::string err;
     // problem data
     DevBuf coef, coef64, raw, rays_a, rays_b, rays64, frames, sel, M, k, grp, grp_off, init_h;
+    // the packing records of the last rship_pack_frames (rship_retime_pixels reads their raw offsets, times and rows),
+    // the readouts of the last re-timing, and host copies of what re-timings have enqueued since the last wait on the
+    // stream (the asynchronous copies read them: released by sync_stream)
+    DevBuf pack_list, retime_ro;
+    std::vector<std::vector<char>> retime_staged;
+    std::vector<uint32_t> h_ray_off; // per table frame: its first ray (rship_retime_pixels checks its table against it)
+    double pack_start = 0, pack_fs = 0;
     DevBuf mo_evals, mo_order; // per slot: evaluations of the last motion launch; launch order (longest first)
     // mo_order is a permutation of each of these slot ranges (the ranges the motion launches of the last call covered);
     // mo_identity: it is the identity, hence a permutation of any range
@@ -259,7 +266,8 @@ int ensure_pinned(rship_ctx* c, size_t bytes) {
 
 // names of the RSHIP_K_* launch kinds: the roctx range around a kind's launches (RSSYNC_ROCTX=1, roctx_ranges.hpp)
 const char* const kKindNames[RSHIP_K_COUNT] = {"rssync:K2 lmeds sweep", "rssync:K1 loss (trials)", "rssync:K3 motion L-BFGS", "rssync:window sums",
-                                               "rssync:K2 GuessMotion search", "rssync:pack frames", "rssync:gyro pipeline", "rssync:K1 loss+gradient"};
+                                               "rssync:K2 GuessMotion search", "rssync:pack frames", "rssync:gyro pipeline", "rssync:K1 loss+gradient",
+                                               "rssync:retime pixels"};
 struct ProfScope {
     rship_ctx* c;
     int kind;
@@ -301,6 +309,7 @@ void prof_collect(rship_ctx* c) {
 int sync_stream(rship_ctx* c) {
     RS_HIP(hipStreamSynchronize(c->stream));
     prof_collect(c);
+    c->retime_staged.clear(); // (every copy a re-timing enqueued has been done)
     return 0;
 }
 
@@ -1078,7 +1087,7 @@ void rship_destroy(rship_ctx* c) {
     if (c->rccl_buf.p) (void)hipFree(c->rccl_buf.p);
     for (auto e : c->pool) (void)hipEventDestroy(e);
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
-    DevBuf* bufs[] = {&c->coef, &c->coef64, &c->raw, &c->rays_a, &c->rays_b, &c->rays64, &c->frames, &c->sel, &c->M, &c->k, &c->grp, &c->grp_off,
+    DevBuf* bufs[] = {&c->pack_list, &c->retime_ro, &c->coef, &c->coef64, &c->raw, &c->rays_a, &c->rays_b, &c->rays64, &c->frames, &c->sel, &c->M, &c->k, &c->grp, &c->grp_off,
                       &c->plan_idx, &c->plan_chunk_off, &c->plan_win_off, &c->chunk_out, &c->win_out, &c->loop_state, &c->kd, &c->kd64, &c->init_h,
                       &c->frame_cost, &c->best_h, &c->costs, &c->part, &c->flags, &c->stats, &c->redo_mask, &c->redo_delays, &c->redo_count, &c->init_delays64, &c->dump,
                       &c->big_scratch, &c->mo_scratch, &c->mo_evals, &c->mo_order,
@@ -1366,6 +1375,35 @@ int rship_upload_raw(rship_ctx* c, const double* host, uint64_t arena_offset, ui
     return 0;
 }
 
+// The frame table to the device (in stream order) and what the spline windows are planned from (own_dims, the spans)
+// to the host state -- rship_pack_frames and rship_retime_pixels alike.  `stable`: the caller's table stays valid until
+// the stream has copied it (rship_retime_pixels' staging); otherwise the copy is waited for where it has to be.
+int install_frame_table(rship_ctx* c, const rship_frame* table, uint32_t n_frames, bool stable) {
+    c->max_span = 0.f;
+    c->max_ends = 0.f;
+    c->own_dims.assign(n_frames, rs::FrameDims{0u, 0.f, 0.f});
+    for (uint32_t i = 0; i < n_frames; ++i) {
+        const float span = rs::frame_span(table[i].tmin, table[i].tmax); // knots a frame touches at one delay
+        if (table[i].n_rays && span > c->max_span) c->max_span = span;
+        // (RSSYNC_FORCE_GENERAL_SPLINE, rounds 1-3: whole pairs only)
+        const float ends = c->force_general ? span : rs::frame_ends(table[i].range_a, table[i].range_b, span);
+        if (table[i].n_rays && ends > c->max_ends) c->max_ends = ends;
+        c->own_dims[i] = rs::FrameDims{table[i].n_rays, span, ends};
+    }
+    update_class_caps(c);
+    if (n_frames && c->force_general) {
+        // RSSYNC_FORCE_GENERAL_SPLINE (rounds 1-3, the sweep's "before" column): whole pairs only, 80-knot windows
+        std::vector<rship_frame> legacy(table, table + n_frames);
+        for (rship_frame& r : legacy) r.range_a = r.range_b = RSHIP_NO_SPLIT;
+        c->max_ends = c->max_span;
+        if (stable) RS_HIP(hipStreamSynchronize(c->stream)); // (the legacy copy is synchronous: the stream's earlier work first)
+        RS_HIP(hipMemcpy(c->frames.p, legacy.data(), (size_t)n_frames * sizeof(rship_frame), hipMemcpyHostToDevice));
+    } else if (n_frames) {
+        RS_HIP(hipMemcpyAsync(c->frames.p, table, (size_t)n_frames * sizeof(rship_frame), hipMemcpyHostToDevice, c->stream));
+    }
+    return 0;
+}
+
 int rship_pack_frames(rship_ctx* c, const rship_frame* table, const rship_pack_frame* pack, uint32_t n_frames,
                       uint64_t total_rays, double start, double fs, uint32_t* bad) {
     DeviceGuard dev_guard(c);
@@ -1374,9 +1412,7 @@ int rship_pack_frames(rship_ctx* c, const rship_frame* table, const rship_pack_f
     c->n_sel = 0;
     c->h_sel.clear();
     c->h_frame_n.assign(n_frames, 0);
-    c->max_span = 0.f;
-    c->max_ends = 0.f;
-    c->own_dims.assign(n_frames, rs::FrameDims{0u, 0.f, 0.f});
+    c->h_ray_off.assign(n_frames, 0);
     c->problem_dims.clear(); // (the host gives them again after packing: rship_set_problem_frames)
     memset(c->cls_off, 0, sizeof(c->cls_off));
     memset(c->cls_max_n, 0, sizeof(c->cls_max_n));
@@ -1392,33 +1428,20 @@ int rship_pack_frames(rship_ctx* c, const rship_frame* table, const rship_pack_f
         if (table[i].n_rays > (uint32_t)rship_max_tracks())
             return set_err(c, "frame has more tracks than the kernels accept (" + std::to_string(rship_max_tracks()) + ")");
         c->h_frame_n[i] = table[i].n_rays;
+        c->h_ray_off[i] = table[i].ray_offset;
         max_n = std::max(max_n, table[i].n_rays);
-        const float span = rs::frame_span(table[i].tmin, table[i].tmax); // knots a frame touches at one delay
-        if (table[i].n_rays && span > c->max_span) c->max_span = span;
-        // (RSSYNC_FORCE_GENERAL_SPLINE, rounds 1-3: whole pairs only)
-        const float ends = c->force_general ? span : rs::frame_ends(table[i].range_a, table[i].range_b, span);
-        if (table[i].n_rays && ends > c->max_ends) c->max_ends = ends;
-        c->own_dims[i] = rs::FrameDims{table[i].n_rays, span, ends};
     }
-    update_class_caps(c);
     const size_t tr = (size_t)total_rays;
     if (ensure(c, c->rays_a, tr ? tr * 16 : 16) || ensure(c, c->rays_b, tr ? tr * 16 : 16) ||
         ensure(c, c->rays64, tr ? tr * 64 : 64))
         return 1;
     if (ensure(c, c->frames, (size_t)n_frames * sizeof(rship_frame) + 64)) return 1;
     c->total_rays = total_rays;
-    if (n_frames && c->force_general) {
-        // RSSYNC_FORCE_GENERAL_SPLINE (rounds 1-3, the sweep's "before" column): whole pairs only, 80-knot windows
-        std::vector<rship_frame> legacy(table, table + n_frames);
-        for (rship_frame& r : legacy) r.range_a = r.range_b = RSHIP_NO_SPLIT;
-        c->max_ends = c->max_span;
-        RS_HIP(hipMemcpy(c->frames.p, legacy.data(), (size_t)n_frames * sizeof(rship_frame), hipMemcpyHostToDevice));
-    } else if (n_frames) {
-        RS_HIP(hipMemcpyAsync(c->frames.p, table, (size_t)n_frames * sizeof(rship_frame), hipMemcpyHostToDevice, c->stream));
-    }
+    if (install_frame_table(c, table, n_frames, false)) return 1;
     uint32_t nb = 0;
     if (n_frames && max_n) {
-        TempBuf dpk, dbad;
+        DevBuf& dpk = c->pack_list; // (kept: rship_retime_pixels reads it)
+        TempBuf dbad;
         if (ensure(c, dpk, (size_t)n_frames * sizeof(rship_pack_frame)) || ensure(c, dbad, 16)) return 1;
         hipError_t e = hipMemcpyAsync(dpk.p, pack, (size_t)n_frames * sizeof(rship_pack_frame), hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess) e = hipMemsetAsync(dbad.p, 0, 16, c->stream);
@@ -1453,6 +1476,53 @@ int rship_pack_frames(rship_ctx* c, const rship_frame* table, const rship_pack_f
     }
     if (bad) *bad = nb;
     c->n_frames = n_frames;
+    c->pack_start = start;
+    c->pack_fs = fs;
+    return 0;
+}
+
+// A new readout for the pixel frames of the table (rssync_c.h: rssync_ext_readout_sweep, rssync_ext_set_readout) without
+// repacking them: the frame table for that readout -- computed by the host exactly as for rship_pack_frames -- is copied to
+// the device and retime_pixels_kernel rewrites the time parts of the packed streams; the ray directions stay.  Everything
+// is enqueued in stream order, nothing is waited for, and the selection, size classes and plan of the sums stay as they
+// are: a batch of sweeps (rship_presync_batch_begin) can re-time between two of its sweeps.  What the windows are planned
+// from (own_dims) follows the new table, as after a repack, so that every sweep plans exactly as it would after
+// rship_pack_frames with that table -- same bits -- and no window is planned for narrower frames than the ones it stages.
+int rship_retime_pixels(rship_ctx* c, const rship_frame* table, const double* ro, uint32_t n_frames) {
+    DeviceGuard dev_guard(c);
+    if (n_frames != c->n_frames) return set_err(c, "retime: the table must have the frames of the last rship_pack_frames");
+    for (uint32_t i = 0; i < n_frames; ++i) {
+        if (table[i].n_rays != c->h_frame_n[i] || table[i].ray_offset != c->h_ray_off[i])
+            return set_err(c, "retime: the table must have the frames of the last rship_pack_frames");
+        if (!std::isfinite(ro[i])) return set_err(c, "retime: non-finite readout");
+    }
+    if (!n_frames) return 0;
+    // host copies that outlive this call: the copies below read them whenever the stream gets there
+    c->retime_staged.emplace_back((size_t)n_frames * (sizeof(rship_frame) + 8));
+    char* stage = c->retime_staged.back().data();
+    std::memcpy(stage, table, (size_t)n_frames * sizeof(rship_frame));
+    std::memcpy(stage + (size_t)n_frames * sizeof(rship_frame), ro, (size_t)n_frames * 8);
+    if (install_frame_table(c, (const rship_frame*)stage, n_frames, true)) return 1;
+    uint32_t max_n = 0;
+    for (uint32_t i = 0; i < n_frames; ++i) max_n = std::max(max_n, c->h_frame_n[i]);
+    if (!max_n) return 0;
+    if (!c->pack_list.p) return set_err(c, "retime: no packed frames");
+    if (ensure(c, c->retime_ro, (size_t)n_frames * 8)) return 1;
+    RS_HIP(hipMemcpyAsync(c->retime_ro.p, stage + (size_t)n_frames * sizeof(rship_frame), (size_t)n_frames * 8, hipMemcpyHostToDevice, c->stream));
+    RetimeParams p{};
+    p.raw = (const double*)c->raw.p;
+    p.pack = (const rship_pack_frame*)c->pack_list.p;
+    p.frames = (const FrameRec*)c->frames.p;
+    p.ro = (const double*)c->retime_ro.p;
+    p.rays_b = (f4*)c->rays_b.p;
+    p.q3 = (double2*)c->rays64.p + 3 * (size_t)c->total_rays;
+    p.start = c->pack_start;
+    p.fs = c->pack_fs;
+    {
+        ProfScope ps(c, RSHIP_K_RETIME);
+        hipLaunchKernelGGL(retime_pixels_kernel, dim3(n_frames, (max_n + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, p);
+    }
+    RS_HIP(hipGetLastError());
     return 0;
 }
 
@@ -2915,6 +2985,7 @@ int rship_rccl_shutdown(rship_ctx* c) {
 int rship_debug_rays(rship_ctx* c, uint32_t frame_index, float* a4, float* b4, uint32_t cap_rays) {
     DeviceGuard dev_guard(c);
     if (frame_index >= c->n_frames) return set_err(c, "debug_rays: index out of range");
+    if (sync_stream(c)) return 1; // (the copies below do not wait for the context's stream: a re-timing may be in flight)
     rship_frame rec;
     hipError_t e = hipMemcpy(&rec, (const rship_frame*)c->frames.p + frame_index, sizeof(rec), hipMemcpyDeviceToHost);
     if (e != hipSuccess) return set_err(c, "debug_rays", e);

@@ -55,6 +55,11 @@ thread_local std::string g_last_error;
 
 } // namespace rssync_host
 
+// The re-timing launcher is referenced WEAKLY: the host solver is also linked against the CPU test double of the device
+// ABI (tests/cpu_device/rship_cpu.cpp), which does not define it.  Without it a new readout is installed by repacking the
+// frames (frames_dirty_), which gives the same bits; librssync_core.so always has it (it links with --no-undefined).
+extern "C" int rship_retime_pixels(rship_ctx* c, const rship_frame* table, const double* ro, uint32_t n_frames) __attribute__((weak));
+
 using rssync_host::g_last_error;
 using rssync_host::g_panic_mode;
 using rssync_host::guarded;
@@ -165,7 +170,22 @@ struct HostFrame {
     bool from_pixels = false;
     double time_a = 0, time_b = 0, rows = 0;
     double lens[9] = {};
+    double qa_min = 0, qa_max = 0, qb_min = 0, qb_max = 0; // per end: extremes of pixel_y / image_rows (with_readout)
 };
+
+// The frame as rssync_ext_set_track_pixels would have noted it with lens.ro = ro (ro >= 0): the row times of an end are
+// time + ro * q with q = pixel_y / image_rows, a non-decreasing function of q for a non-negative readout (in rounded fp64
+// arithmetic too), so their extremes are those of the extreme q's -- the same values the setter's loop over the tracks finds.
+HostFrame with_readout(const HostFrame& f, double ro) {
+    HostFrame g = f;
+    g.lens[0] = ro;
+    if (!f.from_pixels || !f.n) return g;
+    g.a_min = f.time_a + ro * f.qa_min; g.a_max = f.time_a + ro * f.qa_max;
+    g.b_min = f.time_b + ro * f.qb_min; g.b_max = f.time_b + ro * f.qb_max;
+    g.ts_min = std::min(g.a_min, g.b_min);
+    g.ts_max = std::max(g.a_max, g.b_max);
+    return g;
+}
 
 class SyncProblemHip final : public ISyncProblem {
    public:
@@ -191,6 +211,9 @@ class SyncProblemHip final : public ISyncProblem {
     void orientation_sweep(const double* timestamps_s, const double* rates, size_t count,
                            const std::vector<std::string>& orientations, double initial_delay, int64_t frame_begin,
                            int64_t frame_end, double search_step, double search_radius, double* costs, double* delays);
+    void readout_sweep(const double* readouts, size_t n_ro, double initial_delay, int64_t frame_begin, int64_t frame_end,
+                       double search_step, double search_radius, double* costs, double* delays);
+    void set_readout(double ro);
     uint64_t seed = 0x5EED0000ULL;
     int max_outer = 400; // core_private.cpp:309
     bool verbose = true;
@@ -374,6 +397,11 @@ class SyncProblemHip final : public ISyncProblem {
     void combine(size_t rows, size_t n_win, Collect&& collect, double* out);
     void build_spline();
     void pack_frames();
+    rship_frame frame_record(int64_t id, const HostFrame& f, double* base) const;
+    // the devices catch up with the readouts frames_ holds: re-timed (rship_retime_pixels) or, without the launcher, repacked
+    void refresh_readouts();
+    bool can_retime() const { return rship_retime_pixels != nullptr; }
+    std::vector<rship_frame> table_; // the frame table the devices hold (ray offsets local to each shard)
     void accept_gyro(const rship_gyro_result& r);
     void upload_rates(const double* ts, const double* rates, size_t count);
     void integrate_rates(const char* orientation);
@@ -635,11 +663,14 @@ void SyncProblemHip::SetTrackPixels(int64_t frame, double time_a, double time_b,
     for (size_t i = 0; i < count; ++i) {
         rec[4 * i] = px_a[2 * i]; rec[4 * i + 1] = px_a[2 * i + 1];
         rec[4 * i + 2] = px_b[2 * i]; rec[4 * i + 3] = px_b[2 * i + 1];
-        const double tsa = time_a + lens[0] * (px_a[2 * i + 1] / image_rows); // :144
-        const double tsb = time_b + lens[0] * (px_b[2 * i + 1] / image_rows); // :145
-        if (i == 0) { f.a_min = f.a_max = tsa; f.b_min = f.b_max = tsb; }
+        const double qa = px_a[2 * i + 1] / image_rows, qb = px_b[2 * i + 1] / image_rows;
+        const double tsa = time_a + lens[0] * qa; // :144
+        const double tsb = time_b + lens[0] * qb; // :145
+        if (i == 0) { f.a_min = f.a_max = tsa; f.b_min = f.b_max = tsb; f.qa_min = f.qa_max = qa; f.qb_min = f.qb_max = qb; }
         f.a_min = std::min(f.a_min, tsa); f.a_max = std::max(f.a_max, tsa);
         f.b_min = std::min(f.b_min, tsb); f.b_max = std::max(f.b_max, tsb);
+        f.qa_min = std::min(f.qa_min, qa); f.qa_max = std::max(f.qa_max, qa);
+        f.qb_min = std::min(f.qb_min, qb); f.qb_max = std::max(f.qb_max, qb);
     }
     if (count) {
         f.ts_min = std::min(f.a_min, f.b_min);
@@ -839,6 +870,57 @@ void SyncProblemHip::build_spline() {
     spline_dirty_ = false;
 }
 
+// One frame's record of the device table: base knot, parameter range, the two ends' knot ranges (ray_offset: filled in
+// by the caller).  pack_frames and refresh_readouts (a new readout: with_readout) build their tables with it.
+rship_frame SyncProblemHip::frame_record(int64_t id, const HostFrame& f, double* base_out) const {
+    const size_t n = f.n;
+    // (ts - start) * fs is monotonic in ts: its range comes from the range of ts
+    const double xmin = (f.ts_min - start_) * fs_, xmax = (f.ts_max - start_) * fs_;
+    double base = n ? std::floor(xmin) : 0.0;
+    if (!(base > -(double)kKnotClamp)) base = -(double)kKnotClamp;
+    if (base > (double)kKnotClamp) base = (double)kKnotClamp;
+    rship_frame rec{};
+    rec.n_rays = (uint32_t)n;
+    rec.base_knot = (int32_t)base;
+    rec.id = id;
+    rec.tmin64 = n ? xmin - base : 0.0;
+    rec.tmax64 = n ? xmax - base : 0.0;
+    rec.tmin = (float)rec.tmin64;
+    rec.tmax = (float)rec.tmax64;
+    if (f.from_pixels) {
+        // the device recomputes the row times from the pixels with the same fp64 operations; one
+        // ulp of slack on the bounds costs nothing and makes the window independent of that
+        rec.tmin = std::nextafterf(rec.tmin, -std::numeric_limits<float>::infinity());
+        rec.tmax = std::nextafterf(rec.tmax, std::numeric_limits<float>::infinity());
+        rec.tmin64 = std::nextafter(rec.tmin64, -std::numeric_limits<double>::infinity());
+        rec.tmax64 = std::nextafter(rec.tmax64, std::numeric_limits<double>::infinity());
+    }
+    // the knots each END of the pair touches at delay 0, relative to base_knot (rship_frame::range_a / range_b):
+    // floors of the end's smallest / largest offset, taken both on the fp64 value and on its fp32 rounding (the
+    // fp32 stream's offset may round up across a knot), with the same one-ulp slack for pixel frames
+    rec.range_a = rec.range_b = RSHIP_NO_SPLIT;
+    if (n) {
+        auto range = [&](double tlo, double thi) -> uint32_t {
+            double lo64 = (tlo - start_) * fs_ - base, hi64 = (thi - start_) * fs_ - base;
+            float lo32 = (float)lo64, hi32 = (float)hi64;
+            if (f.from_pixels) {
+                lo64 = std::nextafter(lo64, -std::numeric_limits<double>::infinity());
+                hi64 = std::nextafter(hi64, std::numeric_limits<double>::infinity());
+                lo32 = std::nextafterf(lo32, -std::numeric_limits<float>::infinity());
+                hi32 = std::nextafterf(hi32, std::numeric_limits<float>::infinity());
+            }
+            const double lo = std::min(std::floor(lo64), (double)std::floor(lo32));
+            const double hi = std::max(std::floor(hi64), (double)std::floor(hi32));
+            if (!(lo >= 0.0) || !(hi >= lo) || !(hi <= 65000.0)) return RSHIP_NO_SPLIT;
+            return (uint32_t)lo | ((uint32_t)hi << 16);
+        };
+        const uint32_t ra = range(f.a_min, f.a_max), rb = range(f.b_min, f.b_max);
+        if (ra != RSHIP_NO_SPLIT && rb != RSHIP_NO_SPLIT) { rec.range_a = ra; rec.range_b = rb; }
+    }
+    *base_out = base;
+    return rec;
+}
+
 // Device layout of OptData::frame_data (core_private.hpp:21): frames in ascending id order; per
 // ray pair the fp32 streams {ax,bx,ay,by} / {az,bz,ta,tb} (PreSync) and the fp64 streams
 // {ax,bx} {ay,by} {az,bz} {ta,tb} (Sync).  ta/tb carry the spline parameter (ts - start) * fs
@@ -856,49 +938,8 @@ void SyncProblemHip::pack_frames() {
     size_t s = 0;
     for (auto& [id, f] : frames_) {
         const size_t n = f.n;
-        // (ts - start) * fs is monotonic in ts: its range comes from the range of ts
-        const double xmin = (f.ts_min - start_) * fs_, xmax = (f.ts_max - start_) * fs_;
-        double base = n ? std::floor(xmin) : 0.0;
-        if (!(base > -(double)kKnotClamp)) base = -(double)kKnotClamp;
-        if (base > (double)kKnotClamp) base = (double)kKnotClamp;
-        rship_frame rec{};
-        rec.n_rays = (uint32_t)n;
-        rec.base_knot = (int32_t)base;
-        rec.id = id;
-        rec.tmin64 = n ? xmin - base : 0.0;
-        rec.tmax64 = n ? xmax - base : 0.0;
-        rec.tmin = (float)rec.tmin64;
-        rec.tmax = (float)rec.tmax64;
-        if (f.from_pixels) {
-            // the device recomputes the row times from the pixels with the same fp64 operations; one
-            // ulp of slack on the bounds costs nothing and makes the window independent of that
-            rec.tmin = std::nextafterf(rec.tmin, -std::numeric_limits<float>::infinity());
-            rec.tmax = std::nextafterf(rec.tmax, std::numeric_limits<float>::infinity());
-            rec.tmin64 = std::nextafter(rec.tmin64, -std::numeric_limits<double>::infinity());
-            rec.tmax64 = std::nextafter(rec.tmax64, std::numeric_limits<double>::infinity());
-        }
-        // the knots each END of the pair touches at delay 0, relative to base_knot (rship_frame::range_a / range_b):
-        // floors of the end's smallest / largest offset, taken both on the fp64 value and on its fp32 rounding (the
-        // fp32 stream's offset may round up across a knot), with the same one-ulp slack for pixel frames
-        rec.range_a = rec.range_b = RSHIP_NO_SPLIT;
-        if (n) {
-            auto range = [&](double tlo, double thi) -> uint32_t {
-                double lo64 = (tlo - start_) * fs_ - base, hi64 = (thi - start_) * fs_ - base;
-                float lo32 = (float)lo64, hi32 = (float)hi64;
-                if (f.from_pixels) {
-                    lo64 = std::nextafter(lo64, -std::numeric_limits<double>::infinity());
-                    hi64 = std::nextafter(hi64, std::numeric_limits<double>::infinity());
-                    lo32 = std::nextafterf(lo32, -std::numeric_limits<float>::infinity());
-                    hi32 = std::nextafterf(hi32, std::numeric_limits<float>::infinity());
-                }
-                const double lo = std::min(std::floor(lo64), (double)std::floor(lo32));
-                const double hi = std::max(std::floor(hi64), (double)std::floor(hi32));
-                if (!(lo >= 0.0) || !(hi >= lo) || !(hi <= 65000.0)) return RSHIP_NO_SPLIT;
-                return (uint32_t)lo | ((uint32_t)hi << 16);
-            };
-            const uint32_t ra = range(f.a_min, f.a_max), rb = range(f.b_min, f.b_max);
-            if (ra != RSHIP_NO_SPLIT && rb != RSHIP_NO_SPLIT) { rec.range_a = ra; rec.range_b = rb; }
-        }
+        double base = 0;
+        const rship_frame rec = frame_record(id, f, &base);
         rship_pack_frame pf{};
         pf.raw_offset = f.raw_off;
         pf.n_rays = rec.n_rays;
@@ -912,6 +953,7 @@ void SyncProblemHip::pack_frames() {
         cum[s + 1] = cum[s] + n;
         ++s;
     }
+
     // Contiguous blocks of the sorted frame list per device, balanced by ray count, cut at multiples of
     // kChunk frames (the sums over frames are defined on those blocks: DESIGN.md "Sums").
     const size_t S = shards_.size();
@@ -973,9 +1015,176 @@ void SyncProblemHip::pack_frames() {
     // device would (window_plan.hpp: plan_window_frames), so that a frame takes the same spline path wherever it lives
     if (S > 1)
         for (Shard& sh : shards_) hip_check(sh, rship_set_problem_frames(sh.ctx, table.data(), (uint32_t)nf), "problem frames");
+    table_ = std::move(table);
     sel_.clear();
     window_key_.clear();
     frames_dirty_ = false;
+}
+
+// After the readouts of pixel frames in frames_ have changed (with_readout): the devices' tables and packed row times
+// follow -- every shard re-times its own frames, in stream order and without a wait -- or, where the library has no
+// re-timing launcher (the CPU test double), the frames are repacked at the next use.  Same bits either way: the table
+// records come from frame_record as pack_frames makes them, the kernel shares its row-time arithmetic with the packing
+// kernel (kernels/support.hpp: pixel_knot_offset).
+void SyncProblemHip::refresh_readouts() {
+    if (frames_dirty_ || table_.size() != frames_.size()) { frames_dirty_ = true; return; }
+    if (!can_retime()) { frames_dirty_ = true; return; }
+    const size_t nf = frames_.size();
+    std::vector<rship_frame> table(table_);
+    std::vector<double> ro(nf, 0.0);
+    size_t i = 0;
+    for (const auto& [id, f] : frames_) {
+        if (f.from_pixels) {
+            double base = 0;
+            const uint32_t off = table[i].ray_offset;
+            table[i] = frame_record(id, f, &base);
+            table[i].ray_offset = off;
+            ro[i] = f.lens[0];
+        }
+        ++i;
+    }
+    for (Shard& sh : shards_)
+        hip_check(sh, rship_retime_pixels(sh.ctx, table.data() + sh.t0, ro.data() + sh.t0, sh.t1 - sh.t0), "retime pixels");
+    if (shards_.size() > 1)
+        for (Shard& sh : shards_) hip_check(sh, rship_set_problem_frames(sh.ctx, table.data(), (uint32_t)nf), "problem frames");
+    table_ = std::move(table);
+}
+
+// rssync_ext_set_readout: every pixel frame as if set again with lens.ro = ro
+void SyncProblemHip::set_readout(double ro) {
+    rs::RoctxRange roctx_range("rssync:set_readout");
+    if (!std::isfinite(ro) || ro < 0) panic("set-readout: the readout must be a finite, non-negative number of seconds");
+    for (auto& [id, f] : frames_)
+        if (f.from_pixels) f = with_readout(f, ro);
+    sel_.clear();
+    window_key_.clear();
+    refresh_readouts();
+}
+
+// rssync_ext_readout_sweep: for each candidate readout, every frame of [frame_begin, frame_end) re-timed with it, then
+// PreSync (the arg-min rule of PreSync: lexicographic on (cost, delay)); the frames keep their own readouts afterwards.
+// The orientation sweep's pipeline (above): the selection, plan and candidate delays are the same for every readout, so
+// after one selection everything is ENQUEUED -- re-time, sweep, sums, per readout -- into side-by-side result slots
+// (rship_presync_batch_begin), then ONE wait and, with ranks, ONE exchange of the [readout][candidate] matrix.  Between two
+// sweeps only the frame table and the packed row times change (rship_retime_pixels), and with them what the spline windows
+// are planned from: every sweep plans its windows for the frames it stages, exactly as after a repack with that readout.
+// A readout whose sweep flags near-static pairs is redone on its own; without the re-timing launcher (the CPU test double),
+// with more readouts than the batch has status slots, with a candidate list the sweep would slice, or with
+// RSSYNC_SWEEP_PIPELINE=0, every readout goes the plain way: set, PreSync.
+void SyncProblemHip::readout_sweep(const double* readouts, size_t n_ro, double initial_delay, int64_t frame_begin,
+                                   int64_t frame_end, double search_step, double search_radius, double* costs,
+                                   double* delays) {
+    rs::RoctxRange roctx_range("rssync:readout_sweep");
+    if (n_ro < 1) panic("readout sweep: no readouts");
+    for (size_t i = 0; i < n_ro; ++i)
+        if (!std::isfinite(readouts[i]) || readouts[i] < 0)
+            panic("readout sweep: readout " + std::to_string(i) + " is not a finite, non-negative number of seconds");
+    for (const auto& [id, f] : frames_)
+        if (id >= frame_begin && id < frame_end && !f.from_pixels)
+            panic("readout sweep: frame " + std::to_string(id) + " was set as rays (rssync_set_track_result): it has no pixel rows to re-time");
+    ensure_device();
+    // every way out -- a panic in throwing mode included -- leaves each frame with its own readout
+    struct Restore {
+        SyncProblemHip* s;
+        std::map<int64_t, HostFrame> saved;
+        bool armed = true;
+        ~Restore() {
+            if (!armed) return;
+            s->frames_ = std::move(saved);
+            s->frames_dirty_ = true; // (repacked at the next use: nothing is asked of a device that may have failed)
+        }
+    } restore{this, frames_};
+    auto install = [&](double ro) { // the range's frames with readout ro, the others with their own
+        for (auto& [id, f] : frames_)
+            if (id >= frame_begin && id < frame_end) f = with_readout(restore.saved.at(id), ro);
+        refresh_readouts();
+    };
+    auto own = [&]() {
+        frames_ = restore.saved;
+        refresh_readouts();
+    };
+    auto one_by_one = [&](size_t i) {
+        install(readouts[i]);
+        const std::pair<double, double> r = PreSync(initial_delay, frame_begin, frame_end, search_step, search_radius);
+        costs[i] = r.first;
+        delays[i] = r.second;
+    };
+    const char* env_pipeline = std::getenv("RSSYNC_SWEEP_PIPELINE");
+    const bool no_pipeline = env_pipeline && env_pipeline[0] == '0';
+    select(frame_begin, frame_end);
+    std::vector<double> cand; // the candidates are whatever this double loop yields (core_private.cpp:69-70), as in PreSync
+    for (double delay = initial_delay - search_radius; delay < initial_delay + search_radius; delay += search_step) {
+        cand.push_back(delay);
+        if (cand.size() > 50000000) panic("pre-sync: more than 5e7 candidate delays");
+    }
+    if (cand.empty()) panic("pre-sync: empty candidate list");
+    const size_t n = cand.size(), ns = sel_.size(), W = plan_windows_;
+    const size_t slice = std::max<size_t>(64, (size_t)(256u << 20) / (8 * std::max<size_t>(ns, 1)));
+    if (no_pipeline || !can_retime() || n_ro > 255 || n > slice || !ns || (uint64_t)n_ro * n * (W + 1) > (1u << 28)) {
+        for (size_t i = 0; i < n_ro; ++i) one_by_one(i);
+        own();
+        restore.armed = false;
+        return;
+    }
+    std::vector<int32_t> kd(n), kd64(n);
+    std::vector<float> fd(n);
+    std::vector<double> fd64(n);
+    for (size_t i = 0; i < n; ++i) {
+        const DelaySplit sp = split_delay(cand[i], fs_);
+        kd[i] = sp.kd; fd[i] = sp.fd;
+        const DelaySplit64 sp64 = split_delay64(cand[i], fs_);
+        kd64[i] = sp64.kd; fd64[i] = sp64.fd;
+    }
+    for (Shard& sh : shards_) hip_check(sh, rship_presync_batch_begin(sh.ctx, (uint32_t)n_ro, (uint32_t)n), "presync batch");
+    struct CloseBatch { // a panic between here and the collect must not leave the contexts in a batch
+        SyncProblemHip* s;
+        bool armed = true;
+        ~CloseBatch() {
+            if (armed)
+                for (Shard& sh : s->shards_)
+                    if (sh.ctx) (void)rship_presync_batch_begin(sh.ctx, 0, 0);
+        }
+    } close_batch{this};
+    for (size_t i = 0; i < n_ro; ++i) {
+        install(readouts[i]);
+        for (Shard& sh : shards_)
+            hip_check(sh, rship_presync_enqueue(sh.ctx, kd.data(), fd.data(), kd64.data(), fd64.data(), (uint32_t)n, 20 /* core_private.cpp:77 */,
+                                                0u, seed, 0, 0),
+                      "presync");
+    }
+    own(); // (enqueued behind the last sweep: the collect's wait covers it)
+    // ONE wait per device: all readouts' sums, [readout][candidate] rows
+    std::vector<double> all(n_ro * n * W + 1, 0.0);
+    std::vector<uint32_t> flags(n_ro, 0u), fl_sh(n_ro);
+    combine(n_ro * n, W, [&](Shard& sh, double* win, double* chunk) {
+        hip_check(sh, rship_presync_batch_collect(sh.ctx, (uint32_t)n, win, chunk, fl_sh.data()), "presync batch");
+        for (size_t i = 0; i < n_ro; ++i) flags[i] |= fl_sh[i];
+    }, all.data());
+    close_batch.armed = false;
+    // one exchange for the whole matrix; the flag bits ride along as small integers (five per readout)
+    std::vector<double> buf(all.begin(), all.begin() + n_ro * n * W);
+    for (size_t i = 0; i < n_ro; ++i)
+        for (int b = 0; b < 5; ++b) buf.push_back((double)((flags[i] >> b) & 1u));
+    if (distributed()) reduce(buf.data(), buf.size());
+    bool redone = false;
+    for (size_t i = 0; i < n_ro; ++i) {
+        const double* fl = buf.data() + n_ro * n * W + 5 * i;
+        const uint32_t fa = (fl[0] > 0 ? 1u : 0u) | (fl[1] > 0 ? 2u : 0u) | (fl[2] > 0 ? 4u : 0u) | (fl[3] > 0 ? 8u : 0u);
+        if (const char* msg = presync_panic(fa)) panic(msg);
+        if (fl[4] > 0) { // near-static pairs on some rank: this readout once more, with their fp64 form (every rank agrees: the flag was summed)
+            one_by_one(i);
+            redone = true;
+            continue;
+        }
+        const double* c = buf.data() + i * n * W; // (W == 1: select() makes one window)
+        size_t best = 0; // *std::min_element over pair(cost, delay) (core_private.cpp:89)
+        for (size_t k = 1; k < n; ++k)
+            if (std::make_pair(c[k * W], cand[k]) < std::make_pair(c[best * W], cand[best])) best = k;
+        costs[i] = c[best * W];
+        delays[i] = cand[best];
+    }
+    if (redone) own();
+    restore.armed = false;
 }
 
 // Hand a selection to the devices.  `slots` are frame-table indices in slot order (window-major,
@@ -2259,6 +2468,17 @@ int rssync_ext_orientation_sweep(rssync_problem* p, const double* timestamps_s, 
                                    search_radius, costs, delays);
     });
 }
+
+int rssync_ext_readout_sweep(rssync_problem* p, const double* readouts, int n, double initial_delay, int64_t frame_begin,
+                             int64_t frame_end, double search_step, double search_radius, double* costs, double* delays) {
+    return guarded([&] {
+        if (n < 1 || !readouts) panic("readout sweep: no readouts");
+        p->impl->readout_sweep(readouts, (size_t)n, initial_delay, frame_begin, frame_end, search_step, search_radius, costs,
+                               delays);
+    });
+}
+
+int rssync_ext_set_readout(rssync_problem* p, double ro) { return guarded([&] { p->impl->set_readout(ro); }); }
 
 int rssync_ext_frame_rays(rssync_problem* p, int64_t frame, float* a4, float* b4, size_t cap, size_t* n) {
     return guarded([&] {

@@ -99,6 +99,9 @@ SIGNATURES = {
     "rssync_ext_set_gyro_rates": (C.c_int, [C.c_void_p, _PD, _PD, C.c_size_t, C.c_char_p]),
     "rssync_ext_orientation_sweep": (C.c_int, [C.c_void_p, _PD, _PD, C.c_size_t, C.POINTER(C.c_char_p), C.c_int,
                                                C.c_double, C.c_int64, C.c_int64, C.c_double, C.c_double, _PD, _PD]),
+    "rssync_ext_readout_sweep": (C.c_int, [C.c_void_p, _PD, C.c_int, C.c_double, C.c_int64, C.c_int64, C.c_double,
+                                           C.c_double, _PD, _PD]),
+    "rssync_ext_set_readout": (C.c_int, [C.c_void_p, C.c_double]),
     "rssync_ext_frame_rays": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t,
                                         C.POINTER(C.c_size_t)]),
     "rssync_ext_pre_sync_windows": (C.c_int, [C.c_void_p, C.c_double, _PI64, _PI64, C.c_int, C.c_double, C.c_double,
@@ -543,6 +546,20 @@ class SyncProblem:
                                                            _p(costs), _p(delays)))
         return costs, delays
 
+    def readout_sweep(self, readouts, initial_delay, frame_begin, frame_end, search_step, search_radius):
+        """PreSync with every pixel frame of [frame_begin, frame_end) re-timed to each candidate readout (s) ->
+        (costs[n], delays[n]); the lowest cost marks the readout that fits.  The frames keep their own readout."""
+        ro = np.ascontiguousarray(readouts, np.float64).reshape(-1)
+        costs, delays = np.zeros(ro.size), np.zeros(ro.size)
+        self._check(self._lib.rssync_ext_readout_sweep(self._h, _p(ro), ro.size, float(initial_delay), int(frame_begin),
+                                                       int(frame_end), float(search_step), float(search_radius),
+                                                       _p(costs), _p(delays)))
+        return costs, delays
+
+    def set_readout(self, ro):
+        """Every pixel frame as if set again with lens.ro = ro (s)."""
+        self._check(self._lib.rssync_ext_set_readout(self._h, float(ro)))
+
     def frame_rays(self, frame, cap=2048):
         """The packed device streams of one frame: ({ax,bx,ay,by}, {az,bz,ta,tb}) as (n, 4) float32."""
         a4, b4, n = np.zeros((cap, 4), np.float32), np.zeros((cap, 4), np.float32), C.c_size_t()
@@ -639,7 +656,7 @@ class SyncProblem:
         self._check(self._lib.rssync_ext_profile_reset(self._h))
 
     def profile_get(self):
-        names = ["lmeds", "loss", "motion", "reduce", "init", "pixels", "gyro", "loss_grad"]
+        names = ["lmeds", "loss", "motion", "reduce", "init", "pixels", "gyro", "loss_grad", "retime"]
         out = {}
         for i, nm in enumerate(names):
             n, ms = C.c_uint64(), C.c_double()
