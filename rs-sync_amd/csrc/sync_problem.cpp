@@ -17,6 +17,7 @@
 #include "../../include/rssync_hip.h"
 #include "host_errors.hpp"
 #include "roctx_ranges.hpp"
+#include "window_plan.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -769,9 +770,10 @@ void SyncProblemHip::orientation_sweep(const double* ts, const double* rates, si
         if (cand.size() > 50000000) panic("pre-sync: more than 5e7 candidate delays");
     }
     if (cand.empty()) panic("pre-sync: empty candidate list");
-    const size_t n = cand.size(), ns = sel_.size(), W = plan_windows_;
-    const size_t slice = std::max<size_t>(64, (size_t)(256u << 20) / (8 * std::max<size_t>(ns, 1)));
-    if (no_pipeline || n_or < 2 || n_or > 255 || n > slice || !ns || (uint64_t)n_or * n * (W + 1) > (1u << 28)) {
+    const size_t n = cand.size(), W = plan_windows_;
+    // (the route reads only what every rank shares: rs::plan_sweep_pipelined -- a rank that holds no frame of the range
+    // goes the way the others go)
+    if (no_pipeline || n_or < 2 || !rs::plan_sweep_pipelined(n_or, n, W, sel_.size(), frame_begin, frame_end, distributed())) {
         // (one orientation, a candidate list that the sweep would slice, more orientations than there are status records,
         // or RSSYNC_SWEEP_PIPELINE=0 -- rounds 1-5's loop, kept for the A/B and the tests' comparison)
         const std::pair<double, double> r0 = PreSync(initial_delay, frame_begin, frame_end, search_step, search_radius);
@@ -1070,7 +1072,8 @@ void SyncProblemHip::set_readout(double ro) {
 // are planned from: every sweep plans its windows for the frames it stages, exactly as after a repack with that readout.
 // A readout whose sweep flags near-static pairs is redone on its own; without the re-timing launcher (the CPU test double),
 // with more readouts than the batch has status slots, with a candidate list the sweep would slice, or with
-// RSSYNC_SWEEP_PIPELINE=0, every readout goes the plain way: set, PreSync.
+// RSSYNC_SWEEP_PIPELINE=0, every readout goes the plain way: set, PreSync.  With ranks the route is the same on every rank,
+// whichever frames a rank holds (rs::plan_sweep_pipelined).
 void SyncProblemHip::readout_sweep(const double* readouts, size_t n_ro, double initial_delay, int64_t frame_begin,
                                    int64_t frame_end, double search_step, double search_radius, double* costs,
                                    double* delays) {
@@ -1118,9 +1121,8 @@ void SyncProblemHip::readout_sweep(const double* readouts, size_t n_ro, double i
         if (cand.size() > 50000000) panic("pre-sync: more than 5e7 candidate delays");
     }
     if (cand.empty()) panic("pre-sync: empty candidate list");
-    const size_t n = cand.size(), ns = sel_.size(), W = plan_windows_;
-    const size_t slice = std::max<size_t>(64, (size_t)(256u << 20) / (8 * std::max<size_t>(ns, 1)));
-    if (no_pipeline || !can_retime() || n_ro > 255 || n > slice || !ns || (uint64_t)n_ro * n * (W + 1) > (1u << 28)) {
+    const size_t n = cand.size(), W = plan_windows_;
+    if (no_pipeline || !can_retime() || !rs::plan_sweep_pipelined(n_ro, n, W, sel_.size(), frame_begin, frame_end, distributed())) {
         for (size_t i = 0; i < n_ro; ++i) one_by_one(i);
         own();
         restore.armed = false;

@@ -1,6 +1,7 @@
 // window_plan.hpp -- how large the kernels' LDS spline windows are and how many candidate delays a workgroup takes
 // (the host side of DESIGN.md section 3, "Gyro rate").  Pure arithmetic on plain numbers, no HIP: included by
-// rssync_kernels.hip (which supplies the kernels' LDS footprints) and compiled on its own by tests/test_window_plan.py.
+// rssync_kernels.hip (which supplies the kernels' LDS footprints), by sync_problem.cpp (the route of a batched sweep, at
+// the end) and compiled on its own by tests/test_window_plan.py and tests/test_rank_ownership.py.
 //
 // Reference: a frame's rays are evaluated at x = (ts - quats_start + delay) * sample_rate (core_private.cpp:19-20), so
 // a frame pair spans (ts range) * sample_rate knots of the spline and a chunk of candidate delays (its span) more;
@@ -263,6 +264,24 @@ inline size_t exec_region_for(uint32_t cap64, bool compact, uint32_t search_cap)
     const size_t win64 = (size_t)cap64 * (compact ? 64u : 128u);
     const size_t win32 = (size_t)(search_cap ? search_cap : kPlanWinStatic) * 64u;
     return std::max(std::max(win64, win32), (size_t)kPlanExecStage * 8u);
+}
+
+// ---- the route of a batched sweep (sync_problem.cpp: orientation_sweep, readout_sweep) --------------------------------
+// Either ONE pipeline -- every item (orientation, readout) enqueued into its own result slot, one wait, one exchange of
+// n_items * n_cand * n_win + 5 * n_items doubles -- or one PreSync per item (n_items exchanges of n_cand + 4).  With ranks
+// every rank must take the same route, or their exchanges differ in number and size (gloo: an error or a hang; RCCL: a
+// collective that never completes), so the rule reads only what every rank shares: the counts of items, candidates and
+// windows and the range's width.  The device keeps a [candidates][frames] fp64 matrix, so a candidate list longer than
+// PreSync's slice for the selection's frames (2^25 / frames, at least 64) goes the plain way.  One process: the frames of
+// the selection, and an empty selection goes the plain way (nothing to sweep).  Ranks: a rank's selection is its own share
+// of the range, and may be empty -- the range's width bounds every rank's share, and an empty share adds zeros.
+inline bool plan_sweep_pipelined(size_t n_items, size_t n_cand, size_t n_win, size_t n_sel, int64_t frame_begin,
+                                 int64_t frame_end, bool distributed) {
+    if (!distributed && !n_sel) return false;
+    uint64_t frames = distributed ? (frame_end > frame_begin ? (uint64_t)frame_end - (uint64_t)frame_begin : 0u) : n_sel;
+    frames = std::min<uint64_t>(std::max<uint64_t>(frames, 1u), 1ull << 32);
+    const uint64_t slice = std::max<uint64_t>(64u, (uint64_t)(256u << 20) / (8u * frames));
+    return n_items <= 255 && n_cand <= slice && (uint64_t)n_items * n_cand * (n_win + 1) <= (1u << 28);
 }
 
 } // namespace rs
