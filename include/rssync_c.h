@@ -243,6 +243,25 @@ int rssync_ext_set_track_pixels(rssync_problem* p, int64_t frame, double frame_t
  * orientation: telemetry-parser's three-letter axis string ("XYZ" = identity) or NULL. */
 int rssync_ext_set_gyro_rates(rssync_problem* p, const double* timestamps_s, const double* rates, size_t count,
                               const char* orientation);
+/* Gyro CONDITIONING: what rssync_ext_set_gyro_rates and rssync_ext_orientation_sweep do with the uploaded rates
+ * (the reference driver's fixed-rate route, core_testcode.cpp:20-35, with core_support/signal.cpp's gyro_interpolate,
+ * gyro_lowpass and gyro_decimate, all on the device, once per upload).
+ * NULL = off (the default: every raw sample is integrated and handed to the timestamped setter).  Non-NULL, also with
+ * both fields 0 = the uniform route: rates -> uniform grid at the rate rounded to 50 Hz -> [low-pass] -> [decimate] ->
+ * fixed-rate integration -> uniform setter.  The orientations are installed with first_timestamp = time of grid sample 0
+ * + (decimate - 1) / (2 x grid rate), so that decimation does not move the delay.  Recommended pairing for high-rate
+ * logs: lowpass_divider = 4 * decimate.  Errors (before anything is uploaded): lowpass_divider 2 or outside 3 .. 256,
+ * decimate outside 2 .. 64, decimate > 1 with lowpass_divider < 2 * decimate; at the next upload: fewer than three
+ * grid samples left, timestamps out of order, non-finite numbers. */
+typedef struct rssync_gyro_conditioning {
+    int32_t lowpass_divider; /* 0 / 1 = no filter; else 3 .. 256: Butterworth cut-off = grid rate / divider (signal.cpp:5) */
+    int32_t decimate;        /* 0 / 1 = keep every sample; else 2 .. 64: keep every k-th (signal.cpp:53-60) */
+} rssync_gyro_conditioning;
+int rssync_ext_set_gyro_conditioning(rssync_problem* p, const rssync_gyro_conditioning* cfg);
+/* read back what the last set_gyro_rates / orientation_sweep integrated (before the orientation is applied):
+ * rates [n][3] (may be NULL: sizes only), grid rate after decimation, time of sample 0 */
+int rssync_ext_gyro_conditioned(rssync_problem* p, double* rates, size_t cap, size_t* n, double* sample_rate,
+                                double* first_timestamp);
 /* The driver's orientation-guessing sweep (core_testcode.cpp:186-224): for each orientation
  * string, set_gyro_rates(orientation) then PreSync(initial_delay, frame_begin, frame_end, step,
  * radius); costs[i] / delays[i] are that PreSync's result.  Host preparation of orientation i+1

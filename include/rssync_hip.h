@@ -137,6 +137,19 @@ int rship_gyro_rates_integrate(rship_ctx* c, const int32_t axis[3], const double
  * after the batch has been collected: status[i] as rship_gyro_rates_integrate would have returned it. */
 int rship_gyro_rates_integrate_enqueue(rship_ctx* c, const int32_t axis[3], const double sign[3], uint32_t slot, rship_gyro_result* out);
 int rship_gyro_batch_status(rship_ctx* c, uint32_t n, int32_t* status);
+/* CONDITIONING of the uploaded rates, once per rship_gyro_rates_upload (core_support/signal.cpp:3-31, :53-85; the reference
+ * driver's fixed-rate route, core_testcode.cpp:20-35): rates -> uniform grid at the rate rounded to 50 Hz (linear
+ * interpolation) -> zero-phase second-order Butterworth with cut-off grid rate / lowpass_divider (0 / 1: none, else
+ * 3 .. 256) -> every decimate-th sample (0 / 1: all, else 2 .. 64).  The result stays on the device beside the raw stream,
+ * and from here to the next upload rship_gyro_rates_integrate / _integrate_enqueue integrate IT at the fixed rate and
+ * install the orientations as the knots (no resampling).  out: status (RSHIP_GYRO_OK, _BAD_INPUT, _OUT_OF_ORDER with
+ * bad_pos / bad_a / bad_b, _BAD_RATE, _SHORT_GRID: fewer than 3 samples left, _TOO_LARGE), fs = grid rate / decimate,
+ * n_knots = samples left, start = time of sample 0 = grid time + (decimate - 1) / (2 grid rate): a decimated sample
+ * integrated over decimate / rate stands for the mean of the samples that end at it.
+ * rship_gyro_conditioned reads the conditioned rates [n][3] back (rates may be NULL: sizes only).
+ * The host solver references both WEAKLY: a device layer without them refuses the setting. */
+int rship_gyro_rates_condition(rship_ctx* c, int32_t lowpass_divider, int32_t decimate, rship_gyro_result* out);
+int rship_gyro_conditioned(rship_ctx* c, double* rates, uint32_t cap, uint32_t* n, double* sample_rate, double* first_timestamp);
 /* read back: the knots [n_knots][4] / the fp64 table [n_knots][16] (tests, rssync_ext_gyro_knots) */
 int rship_gyro_knots(rship_ctx* c, double* out, uint32_t cap_knots);
 int rship_gyro_table(rship_ctx* c, double* out16, uint32_t cap_knots);

@@ -130,6 +130,128 @@ __global__ __launch_bounds__(256) void gyro_scan_fixup_kernel(double* __restrict
     for (int c = 0; c < 4; ++c) q[4 * (size_t)i + c] = acc[c];
 }
 
+// ---- conditioning: raw rates -> uniform grid -> zero-phase low-pass -> decimation (gyro_signal_math.hpp) -------------
+// Reference: core_support/signal.cpp:3-31 (gyro_lowpass), :53-60 (gyro_decimate), :62-85 (gyro_interpolate) and the
+// fixed-rate integration of core_testcode.cpp:26-34.  Runs once per upload; what it leaves ([m / k][3] rates) is what
+// every orientation integrates.
+
+// the raw stream's own faults: a non-finite number, a timestamp below the one before it
+__global__ __launch_bounds__(256) void gyro_cond_check_kernel(const double* __restrict__ ts, const double* __restrict__ rates, uint32_t n, GyroStatus* st) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const double t = ts[i];
+    if (!(finite64(t) && finite64(rates[3 * (size_t)i]) && finite64(rates[3 * (size_t)i + 1]) && finite64(rates[3 * (size_t)i + 2])))
+        atomicOr(&st->bad_input, 1u);
+    if (i > 0 && ts[i - 1] > t) atomicMin(&st->out_of_order, i);
+}
+
+// one thread per grid point: the rates at time (first_sample + i) / sr
+__global__ __launch_bounds__(256) void gyro_grid_kernel(const double* __restrict__ ts, const double* __restrict__ rates, uint32_t n, double* __restrict__ grid,
+                                                        uint32_t m, int64_t first_sample, int32_t sr) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= m) return;
+    double r[3];
+    rs::interp_rate(ts, rates, n, rs::ugrid_time(first_sample + (int64_t)i, sr), r);
+    for (int c = 0; c < 3; ++c) grid[3 * (size_t)i + c] = r[c];
+}
+
+// One pass of the low-pass (forward, or backward = forward over the reversed array) over in[n][3] -> out[n][3], in != out.
+// A workgroup takes a segment of kScanThreads chunks, a thread one chunk of `chunk` samples and all three axes: the chunk
+// from the state zero, a scan of the chunk end states with the tabulated powers of the companion matrix, the chunk again
+// from its true state in the reference's order of operations.  More than one segment: a first launch with out == nullptr
+// leaves every segment's end state from a zero start in seg_state, gyro_lowpass_carry_kernel turns them into the true
+// ones, and the launch that writes starts segment b's first chunk from seg_state[b - 1].
+struct GyroLowpassParams {
+    const double* in;
+    double* out;
+    double* seg_state; // [segments][3][2]
+    uint32_t n, chunk;
+    int32_t reverse;
+    rs::LowpassCoef k;
+    rs::CarryTable tab;
+};
+
+__global__ __launch_bounds__(kScanThreads) void gyro_lowpass_kernel(GyroLowpassParams p) {
+    __shared__ double s[kScanThreads][6];
+    const uint32_t t = threadIdx.x;
+    const uint64_t seg = (uint64_t)p.chunk * kScanThreads, first = (uint64_t)blockIdx.x * seg;
+    const uint64_t seg_end = first + seg < p.n ? first + seg : p.n;
+    const uint64_t lo64 = first + (uint64_t)t * p.chunk < seg_end ? first + (uint64_t)t * p.chunk : seg_end;
+    const uint32_t lo = (uint32_t)lo64, hi = (uint32_t)(lo64 + p.chunk < seg_end ? lo64 + p.chunk : seg_end);
+    const bool reverse = p.reverse != 0;
+    double start[3][2] = {{0., 0.}, {0., 0.}, {0., 0.}};
+    if (t == 0 && blockIdx.x > 0 && p.out)
+        for (int c = 0; c < 6; ++c) start[c >> 1][c & 1] = p.seg_state[6 * (size_t)(blockIdx.x - 1) + c];
+    double st[3][2];
+    for (int c = 0; c < 6; ++c) st[c >> 1][c & 1] = start[c >> 1][c & 1];
+    rs::lowpass_run(p.k, p.in, nullptr, p.n, reverse, lo, hi, st);
+    for (int c = 0; c < 6; ++c) s[t][c] = st[c >> 1][c & 1];
+    __syncthreads();
+    for (int lvl = 0; lvl < rs::kCarryLevels; ++lvl) {
+        const uint32_t off = 1u << lvl;
+        double from[3][2] = {{0., 0.}, {0., 0.}, {0., 0.}};
+        if (t >= off)
+            for (int c = 0; c < 6; ++c) from[c >> 1][c & 1] = s[t - off][c];
+        __syncthreads();
+        if (t >= off) {
+            rs::carry_step(p.tab.p[lvl], from, st);
+            for (int c = 0; c < 6; ++c) s[t][c] = st[c >> 1][c & 1];
+        }
+        __syncthreads();
+    }
+    if (!p.out) {
+        if (t == kScanThreads - 1)
+            for (int c = 0; c < 6; ++c) p.seg_state[6 * (size_t)blockIdx.x + c] = s[t][c];
+        return;
+    }
+    if (t > 0)
+        for (int c = 0; c < 6; ++c) start[c >> 1][c & 1] = s[t - 1][c];
+    rs::lowpass_run(p.k, p.in, p.out, p.n, reverse, lo, hi, start);
+}
+
+// seg_state[b] <- seg_state[b] + A^segment seg_state[b - 1], b = 1 .. n_seg-1: a few thousand steps at most, one thread
+struct CarryMatrix { double m[4]; };
+__global__ void gyro_lowpass_carry_kernel(double* seg_state, uint32_t n_seg, CarryMatrix P) {
+    double prev[3][2];
+    for (int c = 0; c < 6; ++c) prev[c >> 1][c & 1] = seg_state[c];
+    for (uint32_t b = 1; b < n_seg; ++b) {
+        double v[3][2];
+        for (int c = 0; c < 6; ++c) v[c >> 1][c & 1] = seg_state[6 * (size_t)b + c];
+        rs::carry_step(P.m, prev, v);
+        for (int c = 0; c < 6; ++c) { seg_state[6 * (size_t)b + c] = v[c >> 1][c & 1]; prev[c >> 1][c & 1] = v[c >> 1][c & 1]; }
+    }
+}
+
+// signal.cpp:53-60: sample j = sample j k
+__global__ __launch_bounds__(256) void gyro_decimate_kernel(const double* __restrict__ in, double* __restrict__ out, uint32_t m_out, uint32_t k) {
+    const uint32_t j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= m_out) return;
+    for (int c = 0; c < 3; ++c) out[3 * (size_t)j + c] = in[3 * ((size_t)j * k) + c];
+}
+
+// gyro_rates_kernel for the conditioned stream (core_testcode.cpp:28-33): every sample stands for k / sr seconds
+struct GyroUniformRatesParams {
+    const double* rates; // [n][3] conditioned
+    double* dq;          // [n][4] out; identity at 0
+    uint32_t n;
+    double k, sr;
+    int32_t axis[3];
+    double sign[3];
+};
+
+__global__ __launch_bounds__(256) void gyro_rates_uniform_kernel(GyroUniformRatesParams p) {
+#pragma clang fp contract(off)
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= p.n) return;
+    double d[4] = {1., 0., 0., 0.};
+    if (i > 0) {
+        const double r[3] = {p.rates[3 * (size_t)i], p.rates[3 * (size_t)i + 1], p.rates[3 * (size_t)i + 2]};
+        const double w[3] = {r[p.axis[0]] * p.sign[0] * p.k / p.sr, r[p.axis[1]] * p.sign[1] * p.k / p.sr, r[p.axis[2]] * p.sign[2] * p.k / p.sr};
+        rs::gyro_delta(w, d);
+    }
+    for (int c = 0; c < 4; ++c) p.dq[4 * (size_t)i + c] = d[c];
+}
+
 struct GyroResampleParams {
     const int64_t* ts;   // [n] microseconds
     const double* quats; // [n][4]

@@ -49,6 +49,7 @@
 #include "sync_math.hpp"
 #include "lens_math.hpp"
 #include "gyro_math.hpp"
+#include "gyro_signal_math.hpp"
 #include "window_plan.hpp"
 #include "roctx_ranges.hpp"
 
@@ -116,6 +117,14 @@ struct rship_ctx {
     // gyro pipeline (rship_gyro_*): inputs, intermediate orientations, grid knots, forward-sweep values, status
     DevBuf g_ts, g_rates, g_us, g_dq, g_q, g_knots, g_cf, g_status;
     uint32_t g_n = 0; // samples of the last rship_gyro_rates_upload
+    // conditioning (rship_gyro_rates_condition): the uniform-grid passes' two work arrays, the segment states of the
+    // low-pass, the conditioned rates [gc_n][3] that stay resident beside the raw stream; gc_on: the integrate calls take
+    // the uniform route (cleared by the next upload)
+    DevBuf gc_a, gc_b, gc_seg, gc_rates;
+    bool gc_on = false;
+    uint32_t gc_n = 0, gc_k = 1;
+    double gc_sr = 0, gc_first = 0; // grid rate BEFORE decimation; time of conditioned sample 0 (shifted, rssync_hip.h)
+    double g_first_s = 0, g_last_s = 0;
     // tracker (rship_track_*): two chunk slots (frames + pyramid), the outputs of one call; upload / kernel events per slot
     DevBuf trk_slot[2], trk_out;
     // features (rship_features_track, rship_track_list): per-cell detector results of a chunk, the lists and outputs of a call
@@ -1256,6 +1265,9 @@ int rship_gyro_rates_upload(rship_ctx* c, const double* ts_s, const double* rate
     RS_HIP(hipMemcpyAsync(c->g_rates.p, rates, (size_t)n * 24, hipMemcpyHostToDevice, c->stream));
     RS_HIP(hipStreamSynchronize(c->stream)); // the caller's arrays may go away
     c->g_n = n;
+    c->gc_on = false; // a new stream is raw until it is conditioned
+    c->g_first_s = ts_s[0];
+    c->g_last_s = ts_s[n - 1];
     // the grid only needs the two end timestamps, truncated as the kernel truncates them (core_testcode.cpp:48-50)
     c->g_first_us = (int64_t)(ts_s[0] * 1000000);
     c->g_last_us = (int64_t)(ts_s[n - 1] * 1000000);
@@ -1286,6 +1298,10 @@ int rship_gyro_batch_status(rship_ctx* c, uint32_t n, int32_t* status) {
     if (!n) return 0;
     std::vector<GyroStatus> h(n);
     RS_HIP(hipStreamSynchronize(c->stream));
+    if (c->gc_on) { // the conditioned route: the stream's faults were reported when it was conditioned, the grid is the host's
+        for (uint32_t i = 0; i < n; ++i) status[i] = RSHIP_GYRO_OK;
+        return 0;
+    }
     RS_HIP(hipMemcpy(h.data(), (const GyroStatus*)c->g_status.p + 1, (size_t)n * sizeof(GyroStatus), hipMemcpyDeviceToHost));
     for (uint32_t i = 0; i < n; ++i) {
         rship_gyro_result r{};
@@ -1296,11 +1312,56 @@ int rship_gyro_batch_status(rship_ctx* c, uint32_t n, int32_t* status) {
     return 0;
 }
 namespace {
+// q_0 = dq_0, q_i = normalise(dq_i q_{i-1}) over dq[n][4] -> q[n][4]; tot: scratch for [segments][4] twice
+void launch_quat_scan(rship_ctx* c, const double* dq, double* q, uint32_t n, double* tot) {
+    const uint32_t n_seg = (n + kScanSegment - 1) / kScanSegment;
+    if (n_seg == 1) {
+        hipLaunchKernelGGL(gyro_scan_kernel, dim3(1), dim3(kScanThreads), 0, c->stream, dq, q, n, kScanSegment, (double*)nullptr);
+    } else {
+        // segment totals -> their running products (the same kernel, one workgroup) -> every later segment times its prefix
+        double* pre = tot + 4 * (size_t)n_seg;
+        hipLaunchKernelGGL(gyro_scan_kernel, dim3(n_seg), dim3(kScanThreads), 0, c->stream, dq, q, n, kScanSegment, tot);
+        hipLaunchKernelGGL(gyro_scan_kernel, dim3(1), dim3(kScanThreads), 0, c->stream, (const double*)tot, pre, n_seg, n_seg, (double*)nullptr);
+        hipLaunchKernelGGL(gyro_scan_fixup_kernel, dim3((n - kScanSegment + 255) / 256), dim3(256), 0, c->stream, q, n, kScanSegment, (const double*)pre);
+    }
+}
+
+// the conditioned stream (rship_gyro_rates_condition): fixed-rate integration (core_testcode.cpp:28-33), the orientations
+// ARE the knots (core_private.cpp:135-140), spline solve.  Nothing to wait for: the stream's faults were reported when it
+// was conditioned, and the grid is known on the host.
+int gyro_conditioned_integrate(rship_ctx* c, const int32_t axis[3], const double sign[3], rship_gyro_result* out, uint32_t status_slot, bool wait) {
+    const uint32_t n = c->gc_n;
+    if (n < 2 || n > kMaxKnots) return set_err(c, "gyro: no conditioned rates");
+    if (ensure(c, c->g_dq, (size_t)n * 32) || ensure(c, c->g_knots, (size_t)n * 32) || ensure(c, c->g_status, sizeof(GyroStatus) * kGyroStatusSlots) ||
+        ensure(c, c->g_cf, std::max((size_t)n * 32, (size_t)(n / kScanSegment + 2) * 64)))
+        return 1;
+    GyroUniformRatesParams p{};
+    p.rates = (const double*)c->gc_rates.p; p.dq = (double*)c->g_dq.p; p.n = n;
+    p.k = (double)c->gc_k; p.sr = c->gc_sr;
+    for (int k = 0; k < 3; ++k) { p.axis[k] = axis[k]; p.sign[k] = sign[k]; }
+    {
+        ProfScope ps(c, RSHIP_K_GYRO);
+        hipLaunchKernelGGL(gyro_status_reset_kernel, dim3(1), dim3(1), 0, c->stream, (GyroStatus*)c->g_status.p + status_slot);
+        hipLaunchKernelGGL(gyro_rates_uniform_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, p);
+        launch_quat_scan(c, (const double*)c->g_dq.p, (double*)c->g_knots.p, n, (double*)c->g_cf.p);
+    }
+    RS_HIP(hipGetLastError());
+    const double fs = c->gc_sr / (double)c->gc_k;
+    if (spline_from_knots(c, n, fs)) return 1;
+    *out = rship_gyro_result{};
+    out->status = RSHIP_GYRO_OK;
+    out->fs = fs;
+    out->start = c->gc_first;
+    out->n_knots = n;
+    return wait ? sync_stream(c) : 0;
+}
+
 int gyro_rates_integrate(rship_ctx* c, const int32_t axis[3], const double sign[3], rship_gyro_result* out, uint32_t status_slot, bool wait) {
     const uint32_t n = c->g_n;
     if (n < 2) return set_err(c, "gyro: no rates uploaded");
     for (int k = 0; k < 3; ++k)
         if (axis[k] < 0 || axis[k] > 2) return set_err(c, "gyro: axis out of range");
+    if (c->gc_on) return gyro_conditioned_integrate(c, axis, sign, out, status_slot, wait);
     if (ensure(c, c->g_us, (size_t)n * 8) || ensure(c, c->g_dq, (size_t)n * 32) || ensure(c, c->g_q, (size_t)n * 32) ||
         ensure(c, c->g_status, sizeof(GyroStatus) * kGyroStatusSlots) || ensure(c, c->g_cf, (size_t)(n / kScanSegment + 2) * 64))
         return 1;
@@ -1312,25 +1373,114 @@ int gyro_rates_integrate(rship_ctx* c, const int32_t axis[3], const double sign[
         ProfScope ps(c, RSHIP_K_GYRO);
         hipLaunchKernelGGL(gyro_status_reset_kernel, dim3(1), dim3(1), 0, c->stream, p.st);
         hipLaunchKernelGGL(gyro_rates_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, p);
-        const uint32_t n_seg = (n + kScanSegment - 1) / kScanSegment;
-        if (n_seg == 1) {
-            hipLaunchKernelGGL(gyro_scan_kernel, dim3(1), dim3(kScanThreads), 0, c->stream, (const double*)c->g_dq.p, (double*)c->g_q.p, n,
-                               kScanSegment, (double*)nullptr);
-        } else {
-            // segment totals -> their running products (the same kernel, one workgroup) -> every later segment times its prefix
-            double* tot = (double*)c->g_cf.p; // scratch of the spline solve, not yet in use: [n_seg][4] twice
-            double* pre = tot + 4 * (size_t)n_seg;
-            hipLaunchKernelGGL(gyro_scan_kernel, dim3(n_seg), dim3(kScanThreads), 0, c->stream, (const double*)c->g_dq.p, (double*)c->g_q.p, n,
-                               kScanSegment, tot);
-            hipLaunchKernelGGL(gyro_scan_kernel, dim3(1), dim3(kScanThreads), 0, c->stream, (const double*)tot, pre, n_seg, n_seg, (double*)nullptr);
-            hipLaunchKernelGGL(gyro_scan_fixup_kernel, dim3((n - kScanSegment + 255) / 256), dim3(256), 0, c->stream, (double*)c->g_q.p, n,
-                               kScanSegment, (const double*)pre);
-        }
+        launch_quat_scan(c, (const double*)c->g_dq.p, (double*)c->g_q.p, n, (double*)c->g_cf.p); // (g_cf: scratch of the spline solve, not yet in use)
     }
     RS_HIP(hipGetLastError());
     return resample_and_solve(c, (const int64_t*)c->g_us.p, (const double*)c->g_q.p, n, c->g_first_us, c->g_last_us, out, status_slot, wait);
 }
 } // namespace
+
+// ---- conditioning (gyro_signal_math.hpp, kernels/gyro.hpp): uniform grid -> [low-pass] -> [decimate], once per upload ----
+namespace {
+// one pass of the low-pass over in[m][3] -> out[m][3]
+void launch_lowpass_pass(rship_ctx* c, const double* in, double* out, uint32_t m, bool reverse, const rs::LowpassCoef& k, const rs::CarryTable& tab,
+                         uint32_t chunk) {
+    GyroLowpassParams p{};
+    p.in = in; p.out = out; p.seg_state = (double*)c->gc_seg.p; p.n = m; p.chunk = chunk; p.reverse = reverse ? 1 : 0; p.k = k; p.tab = tab;
+    const uint64_t seg = (uint64_t)chunk * kScanThreads;
+    const uint32_t n_seg = (uint32_t)((m + seg - 1) / seg);
+    if (n_seg > 1) {
+        GyroLowpassParams a = p;
+        a.out = nullptr;
+        CarryMatrix P{};
+        for (int i = 0; i < 4; ++i) P.m[i] = tab.p[rs::kCarryLevels][i];
+        hipLaunchKernelGGL(gyro_lowpass_kernel, dim3(n_seg), dim3(kScanThreads), 0, c->stream, a);
+        hipLaunchKernelGGL(gyro_lowpass_carry_kernel, dim3(1), dim3(1), 0, c->stream, (double*)c->gc_seg.p, n_seg, P);
+    }
+    hipLaunchKernelGGL(gyro_lowpass_kernel, dim3(n_seg), dim3(kScanThreads), 0, c->stream, p);
+}
+} // namespace
+
+int rship_gyro_rates_condition(rship_ctx* c, int32_t lowpass_divider, int32_t decimate, rship_gyro_result* out) {
+    DeviceGuard dev_guard(c);
+    static_assert(kScanThreads == 1 << rs::kCarryLevels, "the carry table covers one workgroup's chunks");
+    const uint32_t n = c->g_n;
+    *out = rship_gyro_result{};
+    c->gc_on = false;
+    if (n < 2) return set_err(c, "gyro: no rates uploaded");
+    const uint32_t k = decimate > 1 ? (uint32_t)decimate : 1u;
+    if (k > 64 || lowpass_divider == 2 || lowpass_divider < 0 || lowpass_divider > 256) return set_err(c, "gyro conditioning: parameter out of range");
+    rs::UniformGrid g{};
+    if (rs::uniform_grid_of(c->g_first_s, c->g_last_s, n, &g) != RS_UGRID_OK) { out->status = RSHIP_GYRO_BAD_RATE; return 0; }
+    out->fs = (double)g.sr / (double)k;
+    out->first_sample = (uint64_t)g.first_sample;
+    const uint64_t m_out = g.count / k;
+    if (m_out < 3) { out->status = RSHIP_GYRO_SHORT_GRID; return 0; }
+    if (g.count > (uint64_t)UINT32_MAX || m_out > kMaxKnots) { out->status = RSHIP_GYRO_TOO_LARGE; return 0; }
+    const uint32_t m = (uint32_t)g.count;
+    const bool filter = lowpass_divider >= 3;
+    const uint32_t chunk = rs::lowpass_chunk_for(m, kScanThreads);
+    const uint64_t seg = (uint64_t)chunk * kScanThreads;
+    if (ensure(c, c->gc_a, (size_t)m * 24) || (filter && ensure(c, c->gc_b, (size_t)m * 24)) || ensure(c, c->gc_rates, (size_t)m_out * 24) ||
+        ensure(c, c->gc_seg, (size_t)((m + seg - 1) / seg + 1) * 48) || ensure(c, c->g_status, sizeof(GyroStatus) * kGyroStatusSlots))
+        return 1;
+    {
+        ProfScope ps(c, RSHIP_K_GYRO);
+        hipLaunchKernelGGL(gyro_status_reset_kernel, dim3(1), dim3(1), 0, c->stream, (GyroStatus*)c->g_status.p);
+        hipLaunchKernelGGL(gyro_cond_check_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, (const double*)c->g_ts.p, (const double*)c->g_rates.p, n,
+                           (GyroStatus*)c->g_status.p);
+        hipLaunchKernelGGL(gyro_grid_kernel, dim3((m + 255) / 256), dim3(256), 0, c->stream, (const double*)c->g_ts.p, (const double*)c->g_rates.p, n,
+                           (double*)c->gc_a.p, m, g.first_sample, g.sr);
+        if (filter) {
+            const rs::LowpassCoef kf = rs::lowpass_coef(lowpass_divider);
+            const rs::CarryTable tab = rs::carry_table(kf, chunk);
+            launch_lowpass_pass(c, (const double*)c->gc_a.p, (double*)c->gc_b.p, m, false, kf, tab, chunk);
+            launch_lowpass_pass(c, (const double*)c->gc_b.p, (double*)c->gc_a.p, m, true, kf, tab, chunk);
+        }
+        hipLaunchKernelGGL(gyro_decimate_kernel, dim3(((uint32_t)m_out + 255) / 256), dim3(256), 0, c->stream, (const double*)c->gc_a.p,
+                           (double*)c->gc_rates.p, (uint32_t)m_out, k);
+    }
+    RS_HIP(hipGetLastError());
+    if (ensure_pinned(c, 64)) return 1;
+    GyroStatus* h = (GyroStatus*)c->pinned;
+    RS_HIP(hipMemcpyAsync(h, c->g_status.p, sizeof(GyroStatus), hipMemcpyDeviceToHost, c->stream));
+    if (sync_stream(c)) return 1;
+    const GyroStatus hs = *h;
+    if (hs.bad_input) { out->status = RSHIP_GYRO_BAD_INPUT; return 0; }
+    if (hs.out_of_order != kNoIndex) {
+        double pair[2];
+        RS_HIP(hipMemcpy(pair, (const double*)c->g_ts.p + (hs.out_of_order - 1), 16, hipMemcpyDeviceToHost));
+        out->status = RSHIP_GYRO_OUT_OF_ORDER;
+        out->bad_pos = hs.out_of_order;
+        out->bad_a = (int64_t)(pair[0] * 1000000);
+        out->bad_b = (int64_t)(pair[1] * 1000000);
+        return 0;
+    }
+    // a decimated sample integrated over k / sr stands for the mean of the k samples that end at it: their centre lies
+    // (k - 1) / (2 sr) before the sample
+    c->gc_first = rs::ugrid_time(g.first_sample, g.sr) + (double)(k - 1) / (2.0 * (double)g.sr);
+    c->gc_sr = (double)g.sr;
+    c->gc_k = k;
+    c->gc_n = (uint32_t)m_out;
+    c->gc_on = true;
+    out->status = RSHIP_GYRO_OK;
+    out->start = c->gc_first;
+    out->n_knots = (uint32_t)m_out;
+    return 0;
+}
+
+int rship_gyro_conditioned(rship_ctx* c, double* rates, uint32_t cap, uint32_t* n, double* sample_rate, double* first_timestamp) {
+    DeviceGuard dev_guard(c);
+    if (!c->gc_on) return set_err(c, "gyro conditioning: no conditioned rates");
+    if (n) *n = c->gc_n;
+    if (sample_rate) *sample_rate = c->gc_sr / (double)c->gc_k;
+    if (first_timestamp) *first_timestamp = c->gc_first;
+    if (!rates) return 0;
+    if (cap < c->gc_n) return set_err(c, "gyro conditioning: buffer too small");
+    RS_HIP(hipStreamSynchronize(c->stream));
+    RS_HIP(hipMemcpy(rates, c->gc_rates.p, (size_t)c->gc_n * 24, hipMemcpyDeviceToHost));
+    return 0;
+}
 
 int rship_gyro_knots(rship_ctx* c, double* out, uint32_t cap_knots) {
     DeviceGuard dev_guard(c);

@@ -61,6 +61,12 @@ thread_local std::string g_last_error;
 // frames (frames_dirty_), which gives the same bits; librssync_core.so always has it (it links with --no-undefined).
 extern "C" int rship_retime_pixels(rship_ctx* c, const rship_frame* table, const double* ro, uint32_t n_frames) __attribute__((weak));
 
+// Gyro conditioning likewise: the product has no CPU path for it, so a device layer without these two refuses the setting
+// (set_gyro_conditioning) instead of emulating it.
+extern "C" int rship_gyro_rates_condition(rship_ctx* c, int32_t lowpass_divider, int32_t decimate, rship_gyro_result* out) __attribute__((weak));
+extern "C" int rship_gyro_conditioned(rship_ctx* c, double* rates, uint32_t cap, uint32_t* n, double* sample_rate, double* first_timestamp)
+    __attribute__((weak));
+
 using rssync_host::g_last_error;
 using rssync_host::g_panic_mode;
 using rssync_host::guarded;
@@ -215,6 +221,8 @@ class SyncProblemHip final : public ISyncProblem {
     void readout_sweep(const double* readouts, size_t n_ro, double initial_delay, int64_t frame_begin, int64_t frame_end,
                        double search_step, double search_radius, double* costs, double* delays);
     void set_readout(double ro);
+    void set_gyro_conditioning(const rssync_gyro_conditioning* cfg);
+    void gyro_conditioned(double* rates, size_t cap, size_t* n, double* sample_rate, double* first_timestamp);
     uint64_t seed = 0x5EED0000ULL;
     int max_outer = 400; // core_private.cpp:309
     bool verbose = true;
@@ -404,6 +412,8 @@ class SyncProblemHip final : public ISyncProblem {
     bool can_retime() const { return rship_retime_pixels != nullptr; }
     std::vector<rship_frame> table_; // the frame table the devices hold (ray offsets local to each shard)
     void accept_gyro(const rship_gyro_result& r);
+    bool cond_on_ = false; // set_gyro_conditioning: the rates setters take the uniform route
+    rssync_gyro_conditioning cond_{0, 0};
     void upload_rates(const double* ts, const double* rates, size_t count);
     void integrate_rates(const char* orientation);
     double* stage_record(int64_t frame, uint64_t n_doubles, HostFrame& f);
@@ -704,6 +714,42 @@ void SyncProblemHip::upload_rates(const double* ts, const double* rates, size_t 
     if (count > (size_t)UINT32_MAX) panic("set-gyro-rates: too many samples");
     if (!std::isfinite(ts[0]) || !std::isfinite(ts[count - 1])) panic("set-gyro-rates: non-finite numbers");
     for (Shard& sh : shards_) hip_check(sh, rship_gyro_rates_upload(sh.ctx, ts, rates, (uint32_t)count), "gyro rates");
+    if (!cond_on_) return;
+    // conditioning, once per upload: every device of the object conditions its own replica, as each integrates its own
+    rship_gyro_result r{};
+    for (Shard& sh : shards_) hip_check(sh, rship_gyro_rates_condition(sh.ctx, cond_.lowpass_divider, cond_.decimate, &r), "gyro conditioning");
+    switch (r.status) {
+        case RSHIP_GYRO_OK: break;
+        case RSHIP_GYRO_SHORT_GRID: n_knots_ = 0; panic("gyro conditioning: fewer than 3 grid samples left after decimation");
+        case RSHIP_GYRO_BAD_RATE: n_knots_ = 0; panic("gyro conditioning: the sample rate rounds to no multiple of 50 Hz");
+        case RSHIP_GYRO_TOO_LARGE: n_knots_ = 0; panic("gyro conditioning: uniform grid too large");
+        default: accept_gyro(r); // non-finite numbers, timestamps out of order: the existing wording
+    }
+}
+
+// The problem-level conditioning setting (rssync_c.h).  Checked here, before anything is uploaded.
+void SyncProblemHip::set_gyro_conditioning(const rssync_gyro_conditioning* cfg) {
+    if (!cfg) { cond_on_ = false; return; }
+    const int32_t div = cfg->lowpass_divider, k = cfg->decimate;
+    if (div == 2) panic("gyro conditioning: lowpass_divider 2 puts both poles on the unit circle; use 3 .. 256");
+    if (div < 0 || div > 256) panic("gyro conditioning: lowpass_divider must be 0, 1 or 3 .. 256");
+    if (k < 0 || k > 64) panic("gyro conditioning: decimate must be 0, 1 or 2 .. 64");
+    if (k > 1 && div < 2 * k) panic("gyro conditioning: decimate " + std::to_string(k) + " needs lowpass_divider >= " + std::to_string(2 * k) +
+                                    " (the cut-off must lie at or below the new Nyquist rate)");
+    if (!rship_gyro_rates_condition || !rship_gyro_conditioned) panic("gyro conditioning: not available in this device layer");
+    cond_ = *cfg;
+    cond_on_ = true;
+}
+
+void SyncProblemHip::gyro_conditioned(double* rates, size_t cap, size_t* n, double* sample_rate, double* first_timestamp) {
+    if (!rship_gyro_conditioned) panic("gyro conditioning: not available in this device layer");
+    uint32_t cnt = 0;
+    Shard& sh = shards_[0];
+    hip_check(sh, rship_gyro_conditioned(sh.ctx, nullptr, 0, &cnt, sample_rate, first_timestamp), "gyro conditioning");
+    if (n) *n = cnt;
+    if (!rates) return;
+    if (cap < cnt) panic("gyro-conditioned: buffer too small");
+    hip_check(sh, rship_gyro_conditioned(sh.ctx, rates, cnt, nullptr, nullptr, nullptr), "gyro conditioning");
 }
 
 void SyncProblemHip::integrate_rates(const char* orientation) {
@@ -2457,6 +2503,14 @@ int rssync_ext_set_track_pixels(rssync_problem* p, int64_t frame, double frame_t
 int rssync_ext_set_gyro_rates(rssync_problem* p, const double* timestamps_s, const double* rates, size_t count,
                               const char* orientation) {
     return guarded([&] { p->impl->SetGyroRates(timestamps_s, rates, count, orientation); });
+}
+
+int rssync_ext_set_gyro_conditioning(rssync_problem* p, const rssync_gyro_conditioning* cfg) {
+    return guarded([&] { p->impl->set_gyro_conditioning(cfg); });
+}
+
+int rssync_ext_gyro_conditioned(rssync_problem* p, double* rates, size_t cap, size_t* n, double* sample_rate, double* first_timestamp) {
+    return guarded([&] { p->impl->gyro_conditioned(rates, cap, n, sample_rate, first_timestamp); });
 }
 
 int rssync_ext_orientation_sweep(rssync_problem* p, const double* timestamps_s, const double* rates, size_t count,

@@ -97,6 +97,8 @@ SIGNATURES = {
     "rssync_ext_set_track_pixels": (C.c_int, [C.c_void_p, C.c_int64, C.c_double, C.c_double, _PD, _PD, C.c_size_t,
                                               C.c_void_p, C.c_double]),
     "rssync_ext_set_gyro_rates": (C.c_int, [C.c_void_p, _PD, _PD, C.c_size_t, C.c_char_p]),
+    "rssync_ext_set_gyro_conditioning": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rssync_ext_gyro_conditioned": (C.c_int, [C.c_void_p, _PD, C.c_size_t, C.POINTER(C.c_size_t), _PD, _PD]),
     "rssync_ext_orientation_sweep": (C.c_int, [C.c_void_p, _PD, _PD, C.c_size_t, C.POINTER(C.c_char_p), C.c_int,
                                                C.c_double, C.c_int64, C.c_int64, C.c_double, C.c_double, _PD, _PD]),
     "rssync_ext_readout_sweep": (C.c_int, [C.c_void_p, _PD, C.c_int, C.c_double, C.c_int64, C.c_int64, C.c_double,
@@ -529,6 +531,27 @@ class SyncProblem:
             raise ValueError("rates must be (n, 3) and timestamps (n,)")
         self._check(self._lib.rssync_ext_set_gyro_rates(self._h, _p(t), _p(r), r.shape[0],
                                                         orientation.encode() if orientation else None))
+
+    def set_gyro_conditioning(self, lowpass_divider=0, decimate=0):
+        """What set_gyro_rates / orientation_sweep do with the rates from now on.  ``set_gyro_conditioning(None)``: off
+        (every raw sample is integrated).  Otherwise the uniform route on the device: rates -> uniform grid at the rate
+        rounded to 50 Hz -> zero-phase Butterworth with cut-off grid rate / lowpass_divider (0: none) -> every
+        decimate-th sample (0: all) -> fixed-rate integration.  Recommended for high-rate logs:
+        ``lowpass_divider = 4 * decimate``."""
+        if lowpass_divider is None:
+            self._check(self._lib.rssync_ext_set_gyro_conditioning(self._h, None))
+            return
+        cfg = (C.c_int32 * 2)(int(lowpass_divider), int(decimate))
+        self._check(self._lib.rssync_ext_set_gyro_conditioning(self._h, C.addressof(cfg)))
+
+    def gyro_conditioned(self):
+        """What the last set_gyro_rates / orientation_sweep integrated under conditioning, before the orientation is
+        applied -> (rates (n, 3), sample rate after decimation, time of sample 0)."""
+        n, fs, t0 = C.c_size_t(), C.c_double(), C.c_double()
+        self._check(self._lib.rssync_ext_gyro_conditioned(self._h, None, 0, C.byref(n), C.byref(fs), C.byref(t0)))
+        out = np.zeros((n.value, 3))
+        self._check(self._lib.rssync_ext_gyro_conditioned(self._h, _p(out), n.value, None, None, None))
+        return out, fs.value, t0.value
 
     def orientation_sweep(self, timestamps_s, rates, orientations, initial_delay, frame_begin, frame_end,
                           search_step, search_radius):
