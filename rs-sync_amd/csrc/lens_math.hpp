@@ -6,10 +6,19 @@
 //                     here in Horner form, see the function)
 //   row_time          :144-145  ts = frame_time + readout * (pixel_y / image_rows)
 //   unit_ray          :147-152  normalise([x_u, y_u, 1])
-// RS_HD like device_math.hpp: the kernel (rays_from_pixels_kernel) inlines these, the CPU test
-// double compiles the same text with g++.  Contraction is switched off so that device, test
-// double and oracle perform the same IEEE operations in the same order; what remains different
-// between them is the libm behind tan/cos (< 1 ulp of fp64, gone after rounding to fp32).
+// RS_HD like device_math.hpp: the kernel (pack_frames_kernel's pixel branch) inlines these, the CPU
+// test double compiles the same text with g++.  Contraction is switched off so that device and
+// test double perform the same IEEE operations in the same order; between them only the libm
+// behind tan/cos differs.  The oracle restates the reference's text instead (expanded powers,
+// error * (1 / slope) where this file has Horner's rule and (model - rd) / slope), so its rays
+// are NOT the same operations: measured on the CPU over 200 000 points per lens, the fp64 unit
+// rays of the two differ by at most 6.9e-16 inside the image (8.9e-16 in a margin of half an
+// image) and no fp32 component differs inside the image; beyond the model's range, where z is
+// ~1e-10, up to 1.2 % of the points differ in fp32 bits, by at most 1.5e-11.  row_time IS the
+// same operations as the oracle's and its results compare bit for bit; knot_offset has no
+// counterpart in the oracle (every route of the library goes through it), so its fp32 results
+// are compared bit for bit with a numpy restatement that rounds every operation on its own
+// (tests/test_pixel_front_door.py, tests/pixel_cases.py: restated_offsets).
 #pragma once
 
 #include <math.h>
