@@ -22,6 +22,8 @@
 //                      driver's grid points (kernels/track.hpp).
 //   corner_*, lkfb_kernel  corner detection per cell and forward-backward LK of the detected corners
 //                      (kernels/features.hpp).
+//   rectify_*_kernel   rolling-shutter rectification of frames with the synced gyro: ray map, per-row rotation
+//                      table, the per-pixel map + bilinear sampler, forward points (kernels/rectify.hpp).
 // Data layout and the roofline that bounds each kernel: DESIGN.md.
 // The kernels live in kernels/*.hpp (one header each, included below); this file holds the
 // device context and the launchers.
@@ -45,9 +47,11 @@
 
 #include "../../include/rssync_hip.h"
 #include "track_hip.h"
+#include "rectify_hip.h"
 #include "device_math.hpp"
 #include "sync_math.hpp"
 #include "lens_math.hpp"
+#include "rectify_math.hpp"
 #include "gyro_math.hpp"
 #include "gyro_signal_math.hpp"
 #include "window_plan.hpp"
@@ -70,6 +74,7 @@ using rs::f4;
 #include "kernels/gyro.hpp"
 #include "kernels/track.hpp"
 #include "kernels/features.hpp"
+#include "kernels/rectify.hpp"
 
 // ===========================================================================
 // host side of the C-ABI
@@ -130,6 +135,11 @@ struct rship_ctx {
     // features (rship_features_track, rship_track_list): per-cell detector results of a chunk, the lists and outputs of a call
     DevBuf ftr_cells, ftr_out;
     hipEvent_t trk_up[2] = {}, trk_k[2] = {};
+    // rectifier (rship_rectify_*): the ray map of the last (lens, width, height) -- rect_key, rect_rays_ok --, two chunk
+    // slots (row tables, host frames in and out), frame times and per-frame counters of a call, one map / point buffer
+    DevBuf rect_rays, rect_slot[2], rect_times, rect_count, rect_tmp;
+    double rect_key[10] = {};
+    bool rect_rays_ok = false;
     int64_t g_first_us = 0, g_last_us = 0;
     std::vector<hipStream_t> loop_streams; // rship_sync_run: one per group of windows
     hipEvent_t loop_ready = nullptr;
@@ -1101,7 +1111,8 @@ void rship_destroy(rship_ctx* c) {
                       &c->frame_cost, &c->best_h, &c->costs, &c->part, &c->flags, &c->stats, &c->redo_mask, &c->redo_delays, &c->redo_count, &c->init_delays64, &c->dump,
                       &c->big_scratch, &c->mo_scratch, &c->mo_evals, &c->mo_order,
                       &c->g_ts, &c->g_rates, &c->g_us, &c->g_dq, &c->g_q, &c->g_knots, &c->g_cf, &c->g_status,
-                      &c->trk_slot[0], &c->trk_slot[1], &c->trk_out, &c->ftr_cells, &c->ftr_out};
+                      &c->trk_slot[0], &c->trk_slot[1], &c->trk_out, &c->ftr_cells, &c->ftr_out,
+                      &c->rect_rays, &c->rect_slot[0], &c->rect_slot[1], &c->rect_times, &c->rect_count, &c->rect_tmp};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     if (c->pinned) (void)hipHostFree(c->pinned);
@@ -3634,6 +3645,243 @@ int rship_track_list(rship_ctx* c, const uint8_t* frames, uint32_t n_frames, siz
     RS_HIP(hipMemcpyAsync(flow, d_flow, n_out * 8, hipMemcpyDeviceToHost, c->stream));
     RS_HIP(hipMemcpyAsync(residual, d_res, n_out * 4, hipMemcpyDeviceToHost, c->stream));
     RS_HIP(hipMemcpyAsync(status, d_st, n_out, hipMemcpyDeviceToHost, c->stream));
+    return sync_stream(c);
+}
+
+} // extern "C"
+
+// ===========================================================================
+// rolling-shutter rectification (kernels/rectify.hpp; declared in rectify_hip.h, called by rectify_api.cpp)
+
+namespace {
+
+// Device bytes the rectifier may hold for host frames on their way in and out and for the row tables: two chunk slots
+// (the one the kernels work in, the one the next upload fills) share it.  Not a knob of the product: a chunk is as many
+// frames as fit, at least one (rship_rectify_frames' budget_bytes exists for the tests).
+constexpr size_t kRectBudget = 256ull << 20;
+constexpr uint32_t kRectMaxChunk = 32768; // frames of a chunk are the grid's z
+
+// host memory, or memory of the context's device (*on_device); another device's pointer is an error, not a copy
+int rect_pointer(rship_ctx* c, const void* p, const char* what, bool* on_device) {
+    hipPointerAttribute_t at{};
+    *on_device = false;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return 0; } // pageable host memory
+    if (at.type == hipMemoryTypeDevice || at.isManaged) {
+        if (at.device != c->device)
+            return set_err(c, std::string("rectify: ") + what + " are in memory of device " + std::to_string(at.device) +
+                                  ", the problem runs on device " + std::to_string(c->device));
+        *on_device = at.type == hipMemoryTypeDevice;
+    }
+    return 0;
+}
+
+int rect_check(rship_ctx* c, const rship_rectify_cfg* g) {
+    if (!g || g->width < 2 || g->height < 2 || g->width > 65536 || g->height > 65536 || g->iterations < 1 || g->iterations > 8 ||
+        g->fill < 0 || g->fill > 255 || !(g->ref_row >= 0.0 && g->ref_row <= (double)g->height))
+        return set_err(c, "rectify: bad configuration");
+    if (c->n_knots < 2 || !c->coef64.p || g->n_knots != c->n_knots) return set_err(c, "rectify: the device holds no spline table of the gyro data");
+    return 0;
+}
+
+rs::Lens rect_lens(const rship_rectify_cfg* g) {
+    return rs::Lens{g->lens[0], g->lens[1], g->lens[2], g->lens[3], g->lens[4], g->lens[5], g->lens[6], g->lens[7], g->lens[8]};
+}
+
+// the ray of every output pixel: computed when the (lens, width, height) of the cached map is another
+int rect_rays(rship_ctx* c, const rship_rectify_cfg* g) {
+    double key[10];
+    for (int i = 0; i < 8; ++i) key[i] = g->lens[i + 1]; // (the readout time does not enter a ray)
+    key[8] = g->width;
+    key[9] = g->height;
+    if (c->rect_rays_ok && !memcmp(key, c->rect_key, sizeof(key))) return 0;
+    c->rect_rays_ok = false;
+    if (ensure(c, c->rect_rays, (size_t)g->width * g->height * sizeof(float4))) return 1;
+    RectRaysArgs A{rect_lens(g), g->width, g->height, (float4*)c->rect_rays.p};
+    hipLaunchKernelGGL(rectify_rays_kernel, dim3((g->width + kRectTW - 1) / kRectTW, (g->height + kRectTH - 1) / kRectTH), dim3(256), 0,
+                       c->stream, A);
+    RS_HIP(hipGetLastError());
+    memcpy(c->rect_key, key, sizeof(key));
+    c->rect_rays_ok = true;
+    return 0;
+}
+
+RectRowsArgs rect_rows_args(rship_ctx* c, const rship_rectify_cfg* g) {
+    RectRowsArgs R{};
+    R.table = (const double*)c->coef64.p;
+    R.start = g->start;
+    R.fs = g->fs;
+    R.ro = g->lens[0];
+    R.delay = g->delay;
+    R.ref_row = g->ref_row;
+    R.n_knots = c->n_knots;
+    R.rows = g->height;
+    return R;
+}
+
+RectArgs rect_args(rship_ctx* c, const rship_rectify_cfg* g) {
+    RectArgs A{};
+    A.rays = (const float4*)c->rect_rays.p;
+    A.lens = rs::RectLensF{(float)g->lens[1], (float)g->lens[2], (float)g->lens[3], (float)g->lens[4],
+                           (float)g->lens[5], (float)g->lens[6], (float)g->lens[7], (float)g->lens[8]};
+    A.width = g->width;
+    A.height = g->height;
+    A.iterations = g->iterations;
+    A.fill = g->fill;
+    return A;
+}
+
+int rect_events(rship_ctx* c) {
+    for (hipEvent_t* e : {&c->trk_up[0], &c->trk_up[1], &c->trk_k[0], &c->trk_k[1]}) // (the tracker's: calls do not overlap)
+        if (!*e) RS_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
+    return 0;
+}
+
+// rows [0, h * cnt) of cnt frames between a pitched user buffer and a packed slot, as one copy where the frames' rows are
+// equally spaced
+int rect_copy(rship_ctx* c, uint8_t* dst, size_t dpitch, size_t dstride, const uint8_t* src, size_t spitch, size_t sstride, uint32_t w,
+              uint32_t h, uint32_t cnt) {
+    if (dstride == dpitch * h && sstride == spitch * h)
+        RS_HIP(hipMemcpy2DAsync(dst, dpitch, src, spitch, w, (size_t)h * cnt, hipMemcpyDefault, c->copy_stream));
+    else
+        for (uint32_t i = 0; i < cnt; ++i)
+            RS_HIP(hipMemcpy2DAsync(dst + (size_t)i * dstride, dpitch, src + (size_t)i * sstride, spitch, w, h, hipMemcpyDefault, c->copy_stream));
+    return 0;
+}
+
+} // namespace
+
+extern "C" {
+
+int rship_rectify_frames(rship_ctx* c, const uint8_t* frames, uint32_t n_frames, size_t pitch, size_t frame_stride,
+                         const double* frame_times, const rship_rectify_cfg* cfg, uint8_t* out, size_t out_pitch, size_t out_stride,
+                         uint64_t* n_outside, size_t budget_bytes) {
+    DeviceGuard dev_guard(c);
+    if (rect_check(c, cfg)) return 1;
+    if (!frames || !out || !frame_times) return set_err(c, "rectify: null pointer");
+    if (!n_frames) return 0;
+    const uint32_t w = cfg->width, h = cfg->height;
+    if (pitch < w || out_pitch < w || (n_frames > 1 && (frame_stride < pitch * h || out_stride < out_pitch * h)))
+        return set_err(c, "rectify: pitch or frame stride too small");
+    bool dev_in = false, dev_out = false;
+    if (rect_pointer(c, frames, "the frames", &dev_in) || rect_pointer(c, out, "the rectified frames", &dev_out)) return 1;
+    const size_t px = (size_t)w * h, tab = (size_t)(h + 1) * 9 * sizeof(float);
+    const size_t per_frame = tab + (dev_in ? 0 : px) + (dev_out ? 0 : px);
+    const size_t budget = budget_bytes ? budget_bytes : kRectBudget;
+    const uint32_t chunk = (uint32_t)std::min<uint64_t>(std::min(n_frames, kRectMaxChunk), std::max<uint64_t>(1, budget / 2 / per_frame));
+    const size_t tab_bytes = ((size_t)chunk * tab + 255) / 256 * 256;
+    const size_t slot_bytes = tab_bytes + (size_t)chunk * (per_frame - tab);
+    for (uint32_t s = 0; s < (n_frames > chunk ? 2u : 1u); ++s)
+        if (ensure(c, c->rect_slot[s], slot_bytes)) return 1;
+    if (ensure(c, c->rect_times, (size_t)n_frames * 8) || ensure(c, c->rect_count, (size_t)n_frames * 8) || rect_events(c)) return 1;
+    RS_HIP(hipMemcpy(c->rect_times.p, frame_times, (size_t)n_frames * 8, hipMemcpyHostToDevice));
+    RS_HIP(hipMemsetAsync(c->rect_count.p, 0, (size_t)n_frames * 8, c->stream));
+    if (rect_rays(c, cfg)) return 1;
+    RectRowsArgs R = rect_rows_args(c, cfg);
+    RectArgs A = rect_args(c, cfg);
+    // chunk j = frames [f0, f0 + cnt) in slot j & 1.  The copy stream carries upload(0), upload(1), download(0), upload(2),
+    // download(1), ...: an upload into a slot follows the download of the chunk that used it before, and waits for that
+    // chunk's kernels; the kernels of a chunk wait for the event recorded after its upload.
+    auto upload = [&](int slot, bool reused, uint32_t f0, uint32_t cnt) -> int {
+        if (reused) RS_HIP(hipStreamWaitEvent(c->copy_stream, c->trk_k[slot], 0));
+        if (!dev_in && rect_copy(c, (uint8_t*)c->rect_slot[slot].p + tab_bytes, w, px, frames + (size_t)f0 * frame_stride, pitch, frame_stride, w, h, cnt))
+            return 1;
+        RS_HIP(hipEventRecord(c->trk_up[slot], c->copy_stream));
+        return 0;
+    };
+    bool used[2] = {false, false};
+    int slot = 0;
+    if (upload(0, false, 0, std::min(chunk, n_frames))) return 1;
+    for (uint32_t f0 = 0; f0 < n_frames;) {
+        const uint32_t cnt = std::min(chunk, n_frames - f0);
+        uint8_t* base = (uint8_t*)c->rect_slot[slot].p;
+        uint8_t* s_in = base + tab_bytes;
+        uint8_t* s_out = s_in + (dev_in ? 0 : (size_t)chunk * px);
+        RS_HIP(hipStreamWaitEvent(c->stream, c->trk_up[slot], 0));
+        R.times = (const double*)c->rect_times.p + f0;
+        R.rows_tab = (float*)base;
+        R.n_frames = cnt;
+        hipLaunchKernelGGL(rectify_rows_kernel, dim3((h + 1 + 255) / 256, cnt), dim3(256), 0, c->stream, R);
+        RS_HIP(hipGetLastError());
+        A.rows_tab = (const float*)base;
+        A.outside = (unsigned long long*)c->rect_count.p + f0;
+        if (dev_in) { A.src = frames + (size_t)f0 * frame_stride; A.src_pitch = pitch; A.src_stride = frame_stride; }
+        else { A.src = s_in; A.src_pitch = w; A.src_stride = px; }
+        if (dev_out) { A.dst = out + (size_t)f0 * out_stride; A.dst_pitch = out_pitch; A.dst_stride = out_stride; }
+        else { A.dst = s_out; A.dst_pitch = w; A.dst_stride = px; }
+        hipLaunchKernelGGL(rectify_kernel<false>, dim3((w + kRectTW - 1) / kRectTW, (h + kRectTH - 1) / kRectTH, cnt), dim3(256), 0, c->stream, A);
+        RS_HIP(hipGetLastError());
+        RS_HIP(hipEventRecord(c->trk_k[slot], c->stream));
+        used[slot] = true;
+        const uint32_t next = f0 + cnt;
+        if (next < n_frames && upload(slot ^ 1, used[slot ^ 1], next, std::min(chunk, n_frames - next))) return 1;
+        if (!dev_out) {
+            RS_HIP(hipStreamWaitEvent(c->copy_stream, c->trk_k[slot], 0));
+            if (rect_copy(c, out + (size_t)f0 * out_stride, out_pitch, out_stride, s_out, w, px, w, h, cnt)) return 1;
+        }
+        f0 = next;
+        slot ^= 1;
+    }
+    if (n_outside) RS_HIP(hipMemcpyAsync(n_outside, c->rect_count.p, (size_t)n_frames * 8, hipMemcpyDeviceToHost, c->stream));
+    RS_HIP(hipStreamSynchronize(c->copy_stream));
+    return sync_stream(c);
+}
+
+int rship_rectify_map(rship_ctx* c, double frame_time, const rship_rectify_cfg* cfg, float* map_xy) {
+    DeviceGuard dev_guard(c);
+    if (rect_check(c, cfg)) return 1;
+    if (!map_xy) return set_err(c, "rectify: null pointer");
+    bool on_dev = false;
+    if (rect_pointer(c, map_xy, "the map", &on_dev)) return 1;
+    const uint32_t w = cfg->width, h = cfg->height;
+    const size_t n = (size_t)w * h;
+    if (ensure(c, c->rect_slot[0], (size_t)(h + 1) * 9 * sizeof(float)) || ensure(c, c->rect_times, 8) ||
+        (!on_dev && ensure(c, c->rect_tmp, n * sizeof(float2))))
+        return 1;
+    RS_HIP(hipMemcpy(c->rect_times.p, &frame_time, 8, hipMemcpyHostToDevice));
+    if (rect_rays(c, cfg)) return 1;
+    RectRowsArgs R = rect_rows_args(c, cfg);
+    R.times = (const double*)c->rect_times.p;
+    R.rows_tab = (float*)c->rect_slot[0].p;
+    R.n_frames = 1;
+    hipLaunchKernelGGL(rectify_rows_kernel, dim3((h + 1 + 255) / 256, 1), dim3(256), 0, c->stream, R);
+    RS_HIP(hipGetLastError());
+    RectArgs A = rect_args(c, cfg);
+    A.rows_tab = (const float*)c->rect_slot[0].p;
+    A.map = on_dev ? (float2*)map_xy : (float2*)c->rect_tmp.p;
+    hipLaunchKernelGGL(rectify_kernel<true>, dim3((w + kRectTW - 1) / kRectTW, (h + kRectTH - 1) / kRectTH, 1), dim3(256), 0, c->stream, A);
+    RS_HIP(hipGetLastError());
+    if (!on_dev) RS_HIP(hipMemcpyAsync(map_xy, c->rect_tmp.p, n * sizeof(float2), hipMemcpyDeviceToHost, c->stream));
+    return sync_stream(c);
+}
+
+int rship_rectify_points(rship_ctx* c, const double* points, size_t count, double frame_time, const rship_rectify_cfg* cfg, double* out) {
+    DeviceGuard dev_guard(c);
+    if (rect_check(c, cfg)) return 1;
+    if (!count) return 0;
+    if (!points || !out) return set_err(c, "rectify: null pointer");
+    if (count > (1ull << 31)) return set_err(c, "rectify: too many points in one call");
+    bool dev_in = false, dev_out = false;
+    if (rect_pointer(c, points, "the points", &dev_in) || rect_pointer(c, out, "the rectified points", &dev_out)) return 1;
+    if (ensure(c, c->rect_tmp, count * 32)) return 1;
+    double* d_in = (double*)c->rect_tmp.p;
+    double* d_out = d_in + 2 * count;
+    RS_HIP(hipMemcpyAsync(d_in, points, count * 16, hipMemcpyDefault, c->stream));
+    RectPointsArgs P{};
+    P.table = (const double*)c->coef64.p;
+    P.points = d_in;
+    P.out = d_out;
+    P.lens = rect_lens(cfg);
+    P.start = cfg->start;
+    P.fs = cfg->fs;
+    P.frame_time = frame_time;
+    P.rows = (double)cfg->height;
+    P.delay = cfg->delay;
+    P.ref_row = cfg->ref_row;
+    P.n_knots = c->n_knots;
+    P.count = count;
+    hipLaunchKernelGGL(rectify_points_kernel, dim3((uint32_t)((count + 255) / 256)), dim3(256), 0, c->stream, P);
+    RS_HIP(hipGetLastError());
+    RS_HIP(hipMemcpyAsync(out, d_out, count * 16, hipMemcpyDefault, c->stream));
     return sync_stream(c);
 }
 

@@ -2112,6 +2112,15 @@ struct rssync_problem {
     bool owns = true;
 };
 
+// for the library's other host files (rectify_hip.h declares it): the spline table of the installed gyro data is on the
+// devices -- the uniform setter leaves building it to the first solve
+namespace rssync_host __attribute__((visibility("hidden"))) {
+void ensure_gyro_table(rssync_problem* p) {
+    if (p->impl->n_knots() < 2) panic("sync: gyro data was not set");
+    p->impl->ensure_spline();
+}
+} // namespace rssync_host
+
 extern "C" {
 
 rssync_problem* rssync_create(void) {

@@ -668,6 +668,24 @@ class SyncProblem:
         from . import features
         return features.features_frames(self, frames, frame_times, lens, first_frame=first_frame, **params)
 
+    def rectify_frames(self, frames, frame_times, lens, delay, **params):
+        """The frames with the rolling-shutter skew removed (include/rssync_rectify.h, rssync_amd.rectify): what a
+        global-shutter camera with the same lens would have seen at the orientation of ref_row's time, from the installed
+        gyro data and `delay`.  frames as in track_points -> (frames of the same kind, n_outside (n,)).  params: ref_row,
+        iterations, fill, out."""
+        from . import rectify
+        return rectify.rectify_frames(self, frames, frame_times, lens, delay, **params)
+
+    def rectify_map(self, width, height, lens, frame_time, delay, **params):
+        """-> (H, W, 2) float32: where rectify_frames looks every output pixel up.  params: ref_row, iterations."""
+        from . import rectify
+        return rectify.rectify_map(self, width, height, lens, frame_time, delay, **params)
+
+    def rectify_points(self, points, width, height, lens, frame_time, delay, ref_row=None):
+        """Tracked points (..., 2) of a rolling-shutter frame -> their positions in the rectified frame (float64)."""
+        from . import rectify
+        return rectify.rectify_points(self, points, width, height, lens, frame_time, delay, ref_row=ref_row)
+
     def device_context(self):
         """rship_ctx* of this problem (include/rssync_hip.h), for kernel-level tools."""
         return self._lib.rssync_ext_device_context(self._h)
