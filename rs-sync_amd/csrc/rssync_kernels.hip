@@ -24,6 +24,8 @@
 //                      (kernels/features.hpp).
 //   rectify_*_kernel   rolling-shutter rectification of frames with the synced gyro: ray map, per-row rotation
 //                      table, the per-pixel map + bilinear sampler, forward points (kernels/rectify.hpp).
+//   stabilize_*_kernel frames rendered at a smoothed or given orientation through an output camera: the Gaussian path,
+//                      the row table against a target, the warp, the border coverage sweep (kernels/stabilize.hpp).
 // Data layout and the roofline that bounds each kernel: DESIGN.md.
 // The kernels live in kernels/*.hpp (one header each, included below); this file holds the
 // device context and the launchers.
@@ -48,10 +50,12 @@
 #include "../../include/rssync_hip.h"
 #include "track_hip.h"
 #include "rectify_hip.h"
+#include "stabilize_hip.h"
 #include "device_math.hpp"
 #include "sync_math.hpp"
 #include "lens_math.hpp"
 #include "rectify_math.hpp"
+#include "stabilize_math.hpp"
 #include "gyro_math.hpp"
 #include "gyro_signal_math.hpp"
 #include "window_plan.hpp"
@@ -75,6 +79,7 @@ using rs::f4;
 #include "kernels/track.hpp"
 #include "kernels/features.hpp"
 #include "kernels/rectify.hpp"
+#include "kernels/stabilize.hpp"
 
 // ===========================================================================
 // host side of the C-ABI
@@ -140,6 +145,9 @@ struct rship_ctx {
     DevBuf rect_rays, rect_slot[2], rect_times, rect_count, rect_tmp;
     double rect_key[10] = {};
     bool rect_rays_ok = false;
+    // stabiliser (rship_stabilize_*): shares the rectifier's buffers and ray map; its own are the path's Gaussian weights
+    // (uploaded once), the target orientations of a call, and the coverage sweep's zooms and counts
+    DevBuf stab_weights, stab_targets, stab_zooms, stab_cover;
     int64_t g_first_us = 0, g_last_us = 0;
     std::vector<hipStream_t> loop_streams; // rship_sync_run: one per group of windows
     hipEvent_t loop_ready = nullptr;
@@ -1112,7 +1120,8 @@ void rship_destroy(rship_ctx* c) {
                       &c->big_scratch, &c->mo_scratch, &c->mo_evals, &c->mo_order,
                       &c->g_ts, &c->g_rates, &c->g_us, &c->g_dq, &c->g_q, &c->g_knots, &c->g_cf, &c->g_status,
                       &c->trk_slot[0], &c->trk_slot[1], &c->trk_out, &c->ftr_cells, &c->ftr_out,
-                      &c->rect_rays, &c->rect_slot[0], &c->rect_slot[1], &c->rect_times, &c->rect_count, &c->rect_tmp};
+                      &c->rect_rays, &c->rect_slot[0], &c->rect_slot[1], &c->rect_times, &c->rect_count, &c->rect_tmp,
+                      &c->stab_weights, &c->stab_targets, &c->stab_zooms, &c->stab_cover};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     if (c->pinned) (void)hipHostFree(c->pinned);
@@ -3662,13 +3671,13 @@ constexpr size_t kRectBudget = 256ull << 20;
 constexpr uint32_t kRectMaxChunk = 32768; // frames of a chunk are the grid's z
 
 // host memory, or memory of the context's device (*on_device); another device's pointer is an error, not a copy
-int rect_pointer(rship_ctx* c, const void* p, const char* what, bool* on_device) {
+int rect_pointer(rship_ctx* c, const void* p, const char* what, bool* on_device, const char* who = "rectify") {
     hipPointerAttribute_t at{};
     *on_device = false;
     if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return 0; } // pageable host memory
     if (at.type == hipMemoryTypeDevice || at.isManaged) {
         if (at.device != c->device)
-            return set_err(c, std::string("rectify: ") + what + " are in memory of device " + std::to_string(at.device) +
+            return set_err(c, std::string(who) + ": " + what + " are in memory of device " + std::to_string(at.device) +
                                   ", the problem runs on device " + std::to_string(c->device));
         *on_device = at.type == hipMemoryTypeDevice;
     }
@@ -3882,6 +3891,289 @@ int rship_rectify_points(rship_ctx* c, const double* points, size_t count, doubl
     hipLaunchKernelGGL(rectify_points_kernel, dim3((uint32_t)((count + 255) / 256)), dim3(256), 0, c->stream, P);
     RS_HIP(hipGetLastError());
     RS_HIP(hipMemcpyAsync(out, d_out, count * 16, hipMemcpyDefault, c->stream));
+    return sync_stream(c);
+}
+
+} // extern "C"
+
+// ===========================================================================
+// stabilisation (kernels/stabilize.hpp; declared in stabilize_hip.h, called by stabilize_api.cpp).  The rectifier's
+// plumbing -- pointer kinds, chunk slots, copy stream, events, ray map -- with an output of its own size.
+
+namespace {
+
+constexpr size_t kStabCoverTables = 64ull << 20; // device bytes of row tables a step of the coverage sweep may hold
+
+int stab_check(rship_ctx* c, const rship_stabilize_cfg* g) {
+    if (!g || g->width < 2 || g->height < 2 || g->width > 65536 || g->height > 65536 || g->out_width < 2 || g->out_height < 2 ||
+        g->out_width > 65536 || g->out_height > 65536 || g->iterations < 1 || g->iterations > 8 || g->fill < 0 || g->fill > 255 ||
+        (g->camera != 0 && g->camera != 1) || !(g->sigma >= 0.0) || !std::isfinite(g->sigma))
+        return set_err(c, "stabilize: bad configuration");
+    if (c->n_knots < 2 || !c->coef64.p || g->n_knots != c->n_knots) return set_err(c, "stabilize: the device holds no spline table of the gyro data");
+    return 0;
+}
+
+// the ray map of the output camera with the lens's distortion: the rectifier's cache, keyed by that camera and the output's size
+int stab_rays(rship_ctx* c, const rship_stabilize_cfg* g) {
+    if (g->camera != 0) return 0;
+    rship_rectify_cfg r{};
+    r.width = g->out_width;
+    r.height = g->out_height;
+    r.lens[0] = g->lens[0];
+    for (int i = 0; i < 4; ++i) r.lens[1 + i] = g->cam[i];
+    for (int i = 5; i < 9; ++i) r.lens[i] = g->lens[i];
+    return rect_rays(c, &r);
+}
+
+// the Gaussian weights of the path's taps, tabulated once in fp64 on the host
+int stab_weights(rship_ctx* c) {
+    if (c->stab_weights.p) return 0;
+    double w[rs::kStabTaps];
+    for (int i = 0; i < rs::kStabTaps; ++i) {
+        const double x = (double)(i - rs::kStabHalfTaps) / rs::kStabTapsPerSigma;
+        w[i] = std::exp(-0.5 * (x * x));
+    }
+    if (ensure(c, c->stab_weights, sizeof(w))) return 1;
+    RS_HIP(hipMemcpy(c->stab_weights.p, w, sizeof(w), hipMemcpyHostToDevice));
+    return 0;
+}
+
+// c->stab_targets <- one unit quaternion per frame: the caller's, or the path at g->sigma of the times in c->rect_times
+int stab_fill_targets(rship_ctx* c, const rship_stabilize_cfg* g, const double* targets, size_t n) {
+    if (ensure(c, c->stab_targets, n * 32)) return 1;
+    if (targets) {
+        RS_HIP(hipMemcpy(c->stab_targets.p, targets, n * 32, hipMemcpyHostToDevice));
+        return 0;
+    }
+    if (stab_weights(c)) return 1;
+    StabPathArgs P{};
+    P.table = (const double*)c->coef64.p;
+    P.times = (const double*)c->rect_times.p;
+    P.weights = (const double*)c->stab_weights.p;
+    P.quats = (double*)c->stab_targets.p;
+    P.start = g->start;
+    P.fs = g->fs;
+    P.t_lo = g->start;
+    P.t_hi = g->start + (double)(c->n_knots - 1) / g->fs;
+    P.ro = g->lens[0];
+    P.delay = g->delay;
+    P.sigma = g->sigma;
+    P.n_knots = c->n_knots;
+    P.n_frames = (uint32_t)n;
+    hipLaunchKernelGGL(stabilize_path_kernel, dim3((uint32_t)n), dim3(64), 0, c->stream, P);
+    RS_HIP(hipGetLastError());
+    return 0;
+}
+
+StabRowsArgs stab_rows_args(rship_ctx* c, const rship_stabilize_cfg* g) {
+    StabRowsArgs R{};
+    R.table = (const double*)c->coef64.p;
+    R.start = g->start;
+    R.fs = g->fs;
+    R.ro = g->lens[0];
+    R.delay = g->delay;
+    R.n_knots = c->n_knots;
+    R.rows = g->height;
+    return R;
+}
+
+rs::RectLensF stab_lens_f(const rship_stabilize_cfg* g) {
+    return rs::RectLensF{(float)g->lens[1], (float)g->lens[2], (float)g->lens[3], (float)g->lens[4],
+                         (float)g->lens[5], (float)g->lens[6], (float)g->lens[7], (float)g->lens[8]};
+}
+
+StabArgs stab_args(rship_ctx* c, const rship_stabilize_cfg* g) {
+    StabArgs A{};
+    A.rays = (const float4*)c->rect_rays.p;
+    A.lens = stab_lens_f(g);
+    A.cam = rs::StabCamF{(float)g->cam[0], (float)g->cam[1], (float)g->cam[2], (float)g->cam[3]};
+    A.y_scale = (float)g->height / (float)g->out_height; // (host division: correctly rounded, 1 when the sizes agree)
+    A.width = g->width;
+    A.height = g->height;
+    A.out_width = g->out_width;
+    A.out_height = g->out_height;
+    A.iterations = g->iterations;
+    A.fill = g->fill;
+    return A;
+}
+
+template <bool MAP>
+void stab_launch(rship_ctx* c, const rship_stabilize_cfg* g, const StabArgs& A, uint32_t cnt) {
+    const dim3 grid((g->out_width + kRectTW - 1) / kRectTW, (g->out_height + kRectTH - 1) / kRectTH, cnt);
+    if (g->camera == 0)
+        hipLaunchKernelGGL((stabilize_kernel<0, MAP>), grid, dim3(256), 0, c->stream, A);
+    else
+        hipLaunchKernelGGL((stabilize_kernel<1, MAP>), grid, dim3(256), 0, c->stream, A);
+}
+
+} // namespace
+
+extern "C" {
+
+int rship_stabilize_path(rship_ctx* c, const double* frame_times, size_t n, const rship_stabilize_cfg* cfg, double* quats) {
+    DeviceGuard dev_guard(c);
+    if (!cfg || !(cfg->sigma >= 0.0) || !std::isfinite(cfg->sigma)) return set_err(c, "stabilize: bad configuration");
+    if (c->n_knots < 2 || !c->coef64.p || cfg->n_knots != c->n_knots) return set_err(c, "stabilize: the device holds no spline table of the gyro data");
+    if (!n) return 0;
+    if (!frame_times || !quats) return set_err(c, "stabilize: null pointer");
+    if (n > 0x7fffffffu) return set_err(c, "stabilize: too many frames");
+    bool on_dev = false;
+    if (rect_pointer(c, quats, "the path's orientations", &on_dev, "stabilize")) return 1;
+    if (ensure(c, c->rect_times, n * 8)) return 1;
+    RS_HIP(hipMemcpy(c->rect_times.p, frame_times, n * 8, hipMemcpyHostToDevice));
+    if (stab_fill_targets(c, cfg, nullptr, n)) return 1;
+    RS_HIP(hipMemcpyAsync(quats, c->stab_targets.p, n * 32, hipMemcpyDefault, c->stream));
+    return sync_stream(c);
+}
+
+int rship_stabilize_frames(rship_ctx* c, const uint8_t* frames, uint32_t n_frames, size_t pitch, size_t frame_stride,
+                           const double* frame_times, const double* targets, const rship_stabilize_cfg* cfg, uint8_t* out,
+                           size_t out_pitch, size_t out_stride, uint64_t* n_outside, size_t budget_bytes) {
+    DeviceGuard dev_guard(c);
+    if (stab_check(c, cfg)) return 1;
+    if (!frames || !out || !frame_times) return set_err(c, "stabilize: null pointer");
+    if (!n_frames) return 0;
+    const uint32_t w = cfg->width, h = cfg->height, ow = cfg->out_width, oh = cfg->out_height;
+    if (pitch < w || out_pitch < ow || (n_frames > 1 && (frame_stride < pitch * h || out_stride < out_pitch * oh)))
+        return set_err(c, "stabilize: pitch or frame stride too small");
+    bool dev_in = false, dev_out = false;
+    if (rect_pointer(c, frames, "the frames", &dev_in, "stabilize") || rect_pointer(c, out, "the stabilised frames", &dev_out, "stabilize")) return 1;
+    const size_t px_in = (size_t)w * h, px_out = (size_t)ow * oh, tab = (size_t)(h + 1) * 9 * sizeof(float);
+    const size_t per_frame = tab + (dev_in ? 0 : px_in) + (dev_out ? 0 : px_out);
+    const size_t budget = budget_bytes ? budget_bytes : kRectBudget;
+    const uint32_t chunk = (uint32_t)std::min<uint64_t>(std::min(n_frames, kRectMaxChunk), std::max<uint64_t>(1, budget / 2 / per_frame));
+    const size_t tab_bytes = ((size_t)chunk * tab + 255) / 256 * 256;
+    const size_t slot_bytes = tab_bytes + (size_t)chunk * (per_frame - tab);
+    for (uint32_t s = 0; s < (n_frames > chunk ? 2u : 1u); ++s)
+        if (ensure(c, c->rect_slot[s], slot_bytes)) return 1;
+    if (ensure(c, c->rect_times, (size_t)n_frames * 8) || ensure(c, c->rect_count, (size_t)n_frames * 8) || rect_events(c)) return 1;
+    RS_HIP(hipMemcpy(c->rect_times.p, frame_times, (size_t)n_frames * 8, hipMemcpyHostToDevice));
+    RS_HIP(hipMemsetAsync(c->rect_count.p, 0, (size_t)n_frames * 8, c->stream));
+    if (stab_fill_targets(c, cfg, targets, n_frames) || stab_rays(c, cfg)) return 1;
+    StabRowsArgs R = stab_rows_args(c, cfg);
+    StabArgs A = stab_args(c, cfg);
+    // the chunk pipeline of rship_rectify_frames: chunk j in slot j & 1, uploads and downloads on the copy stream
+    auto upload = [&](int slot, bool reused, uint32_t f0, uint32_t cnt) -> int {
+        if (reused) RS_HIP(hipStreamWaitEvent(c->copy_stream, c->trk_k[slot], 0));
+        if (!dev_in && rect_copy(c, (uint8_t*)c->rect_slot[slot].p + tab_bytes, w, px_in, frames + (size_t)f0 * frame_stride, pitch, frame_stride, w, h, cnt))
+            return 1;
+        RS_HIP(hipEventRecord(c->trk_up[slot], c->copy_stream));
+        return 0;
+    };
+    bool used[2] = {false, false};
+    int slot = 0;
+    if (upload(0, false, 0, std::min(chunk, n_frames))) return 1;
+    for (uint32_t f0 = 0; f0 < n_frames;) {
+        const uint32_t cnt = std::min(chunk, n_frames - f0);
+        uint8_t* base = (uint8_t*)c->rect_slot[slot].p;
+        uint8_t* s_in = base + tab_bytes;
+        uint8_t* s_out = s_in + (dev_in ? 0 : (size_t)chunk * px_in);
+        RS_HIP(hipStreamWaitEvent(c->stream, c->trk_up[slot], 0));
+        R.times = (const double*)c->rect_times.p + f0;
+        R.targets = (const double*)c->stab_targets.p + (size_t)f0 * 4;
+        R.rows_tab = (float*)base;
+        R.n_frames = cnt;
+        hipLaunchKernelGGL(stabilize_rows_kernel, dim3((h + 1 + 255) / 256, cnt), dim3(256), 0, c->stream, R);
+        RS_HIP(hipGetLastError());
+        A.rows_tab = (const float*)base;
+        A.outside = (unsigned long long*)c->rect_count.p + f0;
+        if (dev_in) { A.src = frames + (size_t)f0 * frame_stride; A.src_pitch = pitch; A.src_stride = frame_stride; }
+        else { A.src = s_in; A.src_pitch = w; A.src_stride = px_in; }
+        if (dev_out) { A.dst = out + (size_t)f0 * out_stride; A.dst_pitch = out_pitch; A.dst_stride = out_stride; }
+        else { A.dst = s_out; A.dst_pitch = ow; A.dst_stride = px_out; }
+        stab_launch<false>(c, cfg, A, cnt);
+        RS_HIP(hipGetLastError());
+        RS_HIP(hipEventRecord(c->trk_k[slot], c->stream));
+        used[slot] = true;
+        const uint32_t next = f0 + cnt;
+        if (next < n_frames && upload(slot ^ 1, used[slot ^ 1], next, std::min(chunk, n_frames - next))) return 1;
+        if (!dev_out) {
+            RS_HIP(hipStreamWaitEvent(c->copy_stream, c->trk_k[slot], 0));
+            if (rect_copy(c, out + (size_t)f0 * out_stride, out_pitch, out_stride, s_out, ow, px_out, ow, oh, cnt)) return 1;
+        }
+        f0 = next;
+        slot ^= 1;
+    }
+    if (n_outside) RS_HIP(hipMemcpyAsync(n_outside, c->rect_count.p, (size_t)n_frames * 8, hipMemcpyDeviceToHost, c->stream));
+    RS_HIP(hipStreamSynchronize(c->copy_stream));
+    return sync_stream(c);
+}
+
+int rship_stabilize_map(rship_ctx* c, double frame_time, const double* target, const rship_stabilize_cfg* cfg, float* map_xy) {
+    DeviceGuard dev_guard(c);
+    if (stab_check(c, cfg)) return 1;
+    if (!map_xy) return set_err(c, "stabilize: null pointer");
+    bool on_dev = false;
+    if (rect_pointer(c, map_xy, "the map", &on_dev, "stabilize")) return 1;
+    const uint32_t h = cfg->height;
+    const size_t n = (size_t)cfg->out_width * cfg->out_height;
+    if (ensure(c, c->rect_slot[0], (size_t)(h + 1) * 9 * sizeof(float)) || ensure(c, c->rect_times, 8) ||
+        (!on_dev && ensure(c, c->rect_tmp, n * sizeof(float2))))
+        return 1;
+    RS_HIP(hipMemcpy(c->rect_times.p, &frame_time, 8, hipMemcpyHostToDevice));
+    if (stab_fill_targets(c, cfg, target, 1) || stab_rays(c, cfg)) return 1;
+    StabRowsArgs R = stab_rows_args(c, cfg);
+    R.times = (const double*)c->rect_times.p;
+    R.targets = (const double*)c->stab_targets.p;
+    R.rows_tab = (float*)c->rect_slot[0].p;
+    R.n_frames = 1;
+    hipLaunchKernelGGL(stabilize_rows_kernel, dim3((h + 1 + 255) / 256, 1), dim3(256), 0, c->stream, R);
+    RS_HIP(hipGetLastError());
+    StabArgs A = stab_args(c, cfg);
+    A.rows_tab = (const float*)c->rect_slot[0].p;
+    A.map = on_dev ? (float2*)map_xy : (float2*)c->rect_tmp.p;
+    stab_launch<true>(c, cfg, A, 1);
+    RS_HIP(hipGetLastError());
+    if (!on_dev) RS_HIP(hipMemcpyAsync(map_xy, c->rect_tmp.p, n * sizeof(float2), hipMemcpyDeviceToHost, c->stream));
+    return sync_stream(c);
+}
+
+int rship_stabilize_coverage(rship_ctx* c, const double* frame_times, uint32_t n_frames, const double* targets,
+                             const rship_stabilize_cfg* cfg, const double* zooms, uint32_t n_zooms, uint32_t* outside) {
+    DeviceGuard dev_guard(c);
+    if (stab_check(c, cfg)) return 1;
+    if (!n_frames || !n_zooms) return 0;
+    if (!frame_times || !zooms || !outside) return set_err(c, "stabilize: null pointer");
+    if (n_zooms > 65535) return set_err(c, "stabilize: more than 65535 zooms in one sweep");
+    const uint32_t h = cfg->height, ow = cfg->out_width, oh = cfg->out_height;
+    const size_t tab = (size_t)(h + 1) * 9 * sizeof(float), counts = (size_t)n_frames * n_zooms * sizeof(uint32_t);
+    const uint32_t chunk = (uint32_t)std::min<uint64_t>(std::min(n_frames, 65535u), std::max<uint64_t>(1, kStabCoverTables / tab));
+    if (ensure(c, c->rect_slot[0], (size_t)chunk * tab) || ensure(c, c->rect_times, (size_t)n_frames * 8) ||
+        ensure(c, c->stab_zooms, (size_t)n_zooms * 8) || ensure(c, c->stab_cover, counts))
+        return 1;
+    RS_HIP(hipMemcpy(c->rect_times.p, frame_times, (size_t)n_frames * 8, hipMemcpyHostToDevice));
+    RS_HIP(hipMemcpy(c->stab_zooms.p, zooms, (size_t)n_zooms * 8, hipMemcpyHostToDevice));
+    RS_HIP(hipMemsetAsync(c->stab_cover.p, 0, counts, c->stream));
+    if (stab_fill_targets(c, cfg, targets, n_frames)) return 1;
+    StabRowsArgs R = stab_rows_args(c, cfg);
+    R.rows_tab = (float*)c->rect_slot[0].p;
+    StabCoverArgs V{};
+    V.rows_tab = (const float*)c->rect_slot[0].p;
+    V.zooms = (const double*)c->stab_zooms.p;
+    V.cam = rs::Lens{0.0, cfg->cam[0], cfg->cam[1], cfg->cam[2], cfg->cam[3], cfg->lens[5], cfg->lens[6], cfg->lens[7], cfg->lens[8]};
+    V.lens = stab_lens_f(cfg);
+    V.y_scale = (float)cfg->height / (float)cfg->out_height;
+    V.width = cfg->width;
+    V.height = h;
+    V.out_width = ow;
+    V.out_height = oh;
+    V.n_border = 2 * (ow + oh) - 4;
+    V.n_zooms = n_zooms;
+    V.iterations = cfg->iterations;
+    V.camera = cfg->camera;
+    // every step on the one stream (a step's tables are read before the next step's rows kernel overwrites them), one wait
+    for (uint32_t f0 = 0; f0 < n_frames; f0 += chunk) {
+        const uint32_t cnt = std::min(chunk, n_frames - f0);
+        R.times = (const double*)c->rect_times.p + f0;
+        R.targets = (const double*)c->stab_targets.p + (size_t)f0 * 4;
+        R.n_frames = cnt;
+        hipLaunchKernelGGL(stabilize_rows_kernel, dim3((h + 1 + 255) / 256, cnt), dim3(256), 0, c->stream, R);
+        RS_HIP(hipGetLastError());
+        V.outside = (uint32_t*)c->stab_cover.p + (size_t)f0 * n_zooms;
+        hipLaunchKernelGGL(stabilize_coverage_kernel, dim3((V.n_border + 255) / 256, n_zooms, cnt), dim3(256), 0, c->stream, V);
+        RS_HIP(hipGetLastError());
+    }
+    RS_HIP(hipMemcpyAsync(outside, c->stab_cover.p, counts, hipMemcpyDeviceToHost, c->stream));
     return sync_stream(c);
 }
 

@@ -686,6 +686,34 @@ class SyncProblem:
         from . import rectify
         return rectify.rectify_points(self, points, width, height, lens, frame_time, delay, ref_row=ref_row)
 
+    def stabilize_path(self, frame_times, ro, delay, sigma, out=None):
+        """-> (n, 4) float64: the Gaussian-smoothed orientation (w, x, y, z) at every frame's centre time
+        (include/rssync_stabilize.h, rssync_amd.stabilize)."""
+        from . import stabilize
+        return stabilize.stabilize_path(self, frame_times, ro, delay, sigma, out=out)
+
+    def stabilize_map(self, width, height, lens, frame_time, delay, **params):
+        """-> (out_height, out_width, 2) float32: where stabilize_frames looks every output pixel up.  params: target,
+        out_size, sigma, zoom, camera, out_camera, iterations."""
+        from . import stabilize
+        return stabilize.stabilize_map(self, width, height, lens, frame_time, delay, **params)
+
+    def stabilize_frames(self, frames, frame_times, lens, delay, **params):
+        """The frames rendered at the smoothed path's orientations, or at `targets` -> (frames of the same kind,
+        n_outside (n,)).  params: targets, out_size, out, sigma, zoom, camera, out_camera, iterations, fill."""
+        from . import stabilize
+        return stabilize.stabilize_frames(self, frames, frame_times, lens, delay, **params)
+
+    def stabilize_coverage(self, width, height, lens, frame_times, delay, zooms, **params):
+        """-> (n_frames, n_zooms) uint32: output border pixels that see past the frame, per frame and zoom."""
+        from . import stabilize
+        return stabilize.stabilize_coverage(self, width, height, lens, frame_times, delay, zooms, **params)
+
+    def stabilize_zoom(self, width, height, lens, frame_times, delay, zooms, **params):
+        """-> the smallest zoom of `zooms` that keeps the borders out of every frame, or None."""
+        from . import stabilize
+        return stabilize.stabilize_zoom(self, width, height, lens, frame_times, delay, zooms, **params)
+
     def device_context(self):
         """rship_ctx* of this problem (include/rssync_hip.h), for kernel-level tools."""
         return self._lib.rssync_ext_device_context(self._h)
