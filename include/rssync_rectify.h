@@ -10,7 +10,9 @@
  * sees the world direction R(q)^T c (core_private.cpp:24-28); a row's time is frame_time + ro * row / rows
  * (core_testcode.cpp:144-145); rssync_lens is the fisheye model of rssync_ext_set_track_pixels.
  *
- * The map, per output pixel: r = unit ray of (u, v) (the driver's undistortion, fp64, kept as fp32); a table of the
+ * The map, per output pixel: r = unit ray of (u, v) (the driver's undistortion, polished with three Newton steps on the
+ * model's true derivative so that it is the inverse of the forward model below for every lens; fp64, kept as fp32); a
+ * table of the
  * rows + 1 matrices M_j = R(q(T + ro * j / rows + delay)) R(q_ref)^T (fp64, kept as fp32); then, from y = v,
  * `iterations` times: M = M_i + (y' - i)(M_(i+1) - M_i) with y' = y clamped to [0, rows - 1] and i = floor(y'),
  * (x, y) = project(M r) with the closed-form forward model theta_d = theta (1 + k1 theta^2 + .. + k4 theta^8).  The last
@@ -20,6 +22,10 @@
  * Sampling is bilinear in fp32 in one fixed order of operations (x0 = min(floor(x), width - 2), fx = x - x0, likewise y;
  * top = p00 + fx (p01 - p00), bot = p10 + fx (p11 - p10), value = top + fy (bot - top), rounded to nearest even), so the
  * bytes are reproducible from the map.  Pixels whose source lies outside get `fill`.
+ *
+ * A pixel the lens cannot image -- its centred, normalised radius lies beyond the model's largest value on (0, pi / 2),
+ * or the inversion is left with a residual above 1e-10 px -- has no ray: its position in rssync_rectify_map is (NaN, NaN),
+ * it gets `fill` and is counted in n_outside; rssync_rectify_points answers (NaN, NaN) for such a point.
  *
  * Frames are n_frames x height rows of width uint8 pixels, rows `pitch` bytes apart, frames `frame_stride` bytes apart;
  * the frames and the result may each be host memory or device memory of the problem's first device

@@ -14,7 +14,10 @@
  * of frames in the call or on how they were chunked.
  *
  * The map of output pixel (u, v).  The output camera is (fx * zoom, fy * zoom, cx, cy) = (fx', fy', cx, cy).  Its ray r:
- * RSSYNC_CAMERA_LENS, the rectifier's ray of that camera with the lens's k1 .. k4 (fp64, kept as fp32);
+ * RSSYNC_CAMERA_LENS, the rectifier's ray of that camera with the lens's k1 .. k4 (the driver's undistortion polished
+ * to the inverse of the forward model; fp64, kept as fp32) -- an output pixel that camera cannot image (rssync_rectify.h)
+ * has no ray: its position in rssync_stabilize_map is (NaN, NaN), it gets `fill`, is counted in n_outside, and as a
+ * border pixel it counts as outside at every zoom of the coverage at which it cannot be imaged;
  * RSSYNC_CAMERA_PINHOLE, ((u - cx) / fx', (v - cy) / fy', 1) normalised, in fp32.  A table of height + 1 matrices
  * M_j = R(q(T + ro * j / height + delay)) R(q_target)^T (fp64, kept as nine fp32 values), where q_target is the path's
  * q_s or the caller's target, normalised in fp64 by the library.  Then, from y = v * (height / out_height) (the factor

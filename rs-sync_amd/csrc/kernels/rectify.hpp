@@ -3,7 +3,8 @@
 // rectify_math.hpp's; the kernels here only say which thread does which pixel, row or point.
 //
 //   rectify_rays_kernel    once per (lens, width, height), cached on the context: the unit ray of every output pixel, fp64
-//                          (the driver's undistortion) stored as float4.
+//                          (the driver's undistortion, polished to the inverse of the forward model; NaN where the lens
+//                          images nothing) stored as float4.
 //   rectify_rows_kernel    once per frame, all frames of a chunk in one launch: the rows + 1 matrices
 //                          R(q(row time + delay)) R(q_ref)^T from the fp64 spline table, nine fp32 values each.
 //   rectify_kernel<MAP>    one thread per output pixel, a workgroup = 64 x 4 pixels: a wave covers one row segment, so its

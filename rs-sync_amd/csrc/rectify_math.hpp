@@ -7,8 +7,9 @@
 //   orientation  core_private.cpp:24-28: the componentwise cubic spline through the gyro knots, renormalised; a camera ray
 //                c at time t sees the world direction R(q(t))^T c (rs::rotate_inv, synth.rotate_inv)
 //   row time     rs::row_time: frame_time + ro * (row / rows)
-//   lens         rs::Lens; pixel -> ray by rs::pixel_to_ray (the driver's Newton inverse), ray -> pixel by the closed-form
-//                fisheye model theta_d = theta (1 + k1 theta^2 + ... + k4 theta^8) (synth.project)
+//   lens         rs::Lens; pixel -> ray by rs::pixel_to_ray (the driver's Newton inverse) polished with the true derivative
+//                (rect_pixel_ray), ray -> pixel by the closed-form fisheye model
+//                theta_d = theta (1 + k1 theta^2 + ... + k4 theta^8) (synth.project)
 //
 // The map of an output pixel (u, v) of the rectified frame (a global-shutter camera at q_ref):
 //   r      = ray(u, v)                                           fp64, stored fp32   (rect_pixel_ray)
@@ -80,6 +81,21 @@ RS_LHD void rect_row_matrix(const double* table, int n_knots, double start, doub
 // unit ray of a pixel position.  The driver's undistortion answers the image CENTRE for the pixel position (0, 0) itself
 // (core_testcode.cpp:64 tests the pixel, not the centred position); a map has that pixel, so it is asked for as pixel
 // (1, 0) of the same lens with its centre one pixel further right: the same centred position.
+//
+// The driver's nine steps use a slope with 8 k4 where the derivative has 9 k4, so for a lens with a large k4 they stop short
+// of the fixed point (1.3e-2 px at the border of a 1520 x 2704 image with k = 0.03, 0.06, -0.06, 0.02), and for a position
+// the lens cannot image -- rd beyond the model's largest value on [0, pi/2] -- they park theta near pi/2.  A map needs the
+// inverse of rect_project_*, so theta is polished here with kRectPolishSteps plain Newton steps on the true derivative
+// and the ray rebuilt from it: on the CPU, over every pixel of eight lenses at 1520 x 2704, two steps leave
+// |model(theta) - rd| * max(fx, fy) <= 7.5e-13 px and a third changes nothing; three are taken.  A position whose polished
+// theta lies outside (0, pi/2), or whose residual stays above kRectRayResidualPx, gets a NaN ray: rect_map_pixel and
+// rect_project_d carry the NaN, and rect_inside is false for it.  kRectRayResidualPx = 1e-10 px lies between what fp64
+// converges to (1e-12 px above) and what an fp32 pixel coordinate resolves (7.6e-6 px at 64 .. 128); positions the lens
+// cannot image miss it by orders of magnitude (their residual is rd - max model, in pixels).  Within 1e-9 of the centre
+// (the driver's own branch: the ray is (xn, yn, 1) normalised whatever theta is) nothing is polished.
+constexpr int kRectPolishSteps = 3;
+constexpr double kRectRayResidualPx = 1e-10;
+
 RS_LHD void rect_pixel_ray(const Lens& lens, double px, double py, double* ray) {
     double ts;
     Lens l = lens;
@@ -88,6 +104,27 @@ RS_LHD void rect_pixel_ray(const Lens& lens, double px, double py, double* ray) 
         l.cx = lens.cx + 1.0;
     }
     pixel_to_ray(l, px, py, 0.0, 1.0, ray, &ts);
+    const double xn = (px - l.cx) / l.fx, yn = (py - l.cy) / l.fy;
+    const double rd = sqrt(xn * xn + yn * yn);
+    if (rd < 1e-9) return;
+    double th = atan2(sqrt(ray[0] * ray[0] + ray[1] * ray[1]), ray[2]);
+    for (int step = 0; step < kRectPolishSteps; ++step) {
+        const double q = th * th;
+        const double model = th * (1. + q * (l.k1 + q * (l.k2 + q * (l.k3 + q * l.k4))));
+        const double slope = 1. + q * (3. * l.k1 + q * (5. * l.k2 + q * (7. * l.k3 + q * (9. * l.k4))));
+        th = th - (model - rd) / slope;
+    }
+    const double q = th * th;
+    const double res = fabs(th * (1. + q * (l.k1 + q * (l.k2 + q * (l.k3 + q * l.k4)))) - rd);
+    const double fmax_ = fabs(l.fx) > fabs(l.fy) ? fabs(l.fx) : fabs(l.fy);
+    if (!(th > 0.0 && th < 1.57079632679489661923 && res * fmax_ <= kRectRayResidualPx)) {
+        ray[0] = ray[1] = ray[2] = NAN;
+        return;
+    }
+    const double s = sin(th) / rd;
+    ray[0] = xn * s;
+    ray[1] = yn * s;
+    ray[2] = cos(th);
 }
 
 // the lens in fp32, for the iteration
@@ -122,7 +159,7 @@ RS_LHD void rect_map_pixel(const float* rows_tab, int rows, const RectLensF& L, 
     float x = 0.0f, y = v;
     const float top = (float)(rows - 1);
     for (int it = 0; it < iterations; ++it) {
-        float yc = y < top ? y : top;   // (a NaN takes the last row: its position stays NaN and is outside)
+        float yc = y < top ? y : top;   // (a NaN, or a NaN ray, takes the last row: its position is NaN and is outside)
         yc = yc > 0.0f ? yc : 0.0f;
         const float fl = floorf(yc);
         const float f = yc - fl;

@@ -8,8 +8,12 @@
             device's bytes
   forward_points   rolling-shutter position -> rectified position, closed form, float64
 
-The rays come from synth.unproject (plain Newton with the true derivative, 40 steps), not from a restatement of the
-driver's nine-step schedule the device runs: the two inverses are independent and agree far below a float32 ulp.
+The rays come from synth.unproject (plain Newton with the true derivative, 40 steps): the inverse of the forward model.
+The device starts from the driver's nine-step schedule, whose slope has 8 k4 for 9 k4; that schedule alone agrees with the
+true inverse far below a float32 ulp for synth.LENS, but not for every lens (tests/pixel_cases.py's `wide`: 1.3e-2 px at
+the border of 1520 x 2704), so rect_pixel_ray polishes it with the true derivative -- tests/warp_cases.py holds the
+device to this reference for eight lenses.  Positions a lens cannot image get a clipped, meaningless ray here and a NaN
+ray on the device: compare in range only (warp_cases.range_masks).
 """
 import functools
 
