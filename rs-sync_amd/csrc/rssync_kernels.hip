@@ -26,6 +26,8 @@
 //                      table, the per-pixel map + bilinear sampler, forward points (kernels/rectify.hpp).
 //   stabilize_*_kernel frames rendered at a smoothed or given orientation through an output camera: the Gaussian path,
 //                      the row table against a target, the warp, the border coverage sweep (kernels/stabilize.hpp).
+//   color_*_kernel     NV12, I420 and RGBA32 frames stabilised with all planes of a frame in one launch: both row tables,
+//                      the 4:2:0 warp per chroma sample with its 2 x 2 luma pixels, the RGBA warp (kernels/color.hpp).
 // Data layout and the roofline that bounds each kernel: DESIGN.md.
 // The kernels live in kernels/*.hpp (one header each, included below); this file holds the
 // device context and the launchers.
@@ -51,11 +53,13 @@
 #include "track_hip.h"
 #include "rectify_hip.h"
 #include "stabilize_hip.h"
+#include "color_hip.h"
 #include "device_math.hpp"
 #include "sync_math.hpp"
 #include "lens_math.hpp"
 #include "rectify_math.hpp"
 #include "stabilize_math.hpp"
+#include "color_math.hpp"
 #include "gyro_math.hpp"
 #include "gyro_signal_math.hpp"
 #include "window_plan.hpp"
@@ -80,6 +84,7 @@ using rs::f4;
 #include "kernels/features.hpp"
 #include "kernels/rectify.hpp"
 #include "kernels/stabilize.hpp"
+#include "kernels/color.hpp"
 
 // ===========================================================================
 // host side of the C-ABI
@@ -148,6 +153,11 @@ struct rship_ctx {
     // stabiliser (rship_stabilize_*): shares the rectifier's buffers and ray map; its own are the path's Gaussian weights
     // (uploaded once), the target orientations of a call, and the coverage sweep's zooms and counts
     DevBuf stab_weights, stab_targets, stab_zooms, stab_cover;
+    // colour front (rship_color_*): shares all of the above; its own is a second cached ray map, the chroma output camera's,
+    // keyed as the first is, so that a 4:2:0 call of one configuration after another computes neither
+    DevBuf rect_rays_c;
+    double rect_key_c[10] = {};
+    bool rect_rays_c_ok = false;
     int64_t g_first_us = 0, g_last_us = 0;
     std::vector<hipStream_t> loop_streams; // rship_sync_run: one per group of windows
     hipEvent_t loop_ready = nullptr;
@@ -1121,7 +1131,7 @@ void rship_destroy(rship_ctx* c) {
                       &c->g_ts, &c->g_rates, &c->g_us, &c->g_dq, &c->g_q, &c->g_knots, &c->g_cf, &c->g_status,
                       &c->trk_slot[0], &c->trk_slot[1], &c->trk_out, &c->ftr_cells, &c->ftr_out,
                       &c->rect_rays, &c->rect_slot[0], &c->rect_slot[1], &c->rect_times, &c->rect_count, &c->rect_tmp,
-                      &c->stab_weights, &c->stab_targets, &c->stab_zooms, &c->stab_cover};
+                      &c->stab_weights, &c->stab_targets, &c->stab_zooms, &c->stab_cover, &c->rect_rays_c};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     if (c->pinned) (void)hipHostFree(c->pinned);
@@ -3696,23 +3706,26 @@ rs::Lens rect_lens(const rship_rectify_cfg* g) {
     return rs::Lens{g->lens[0], g->lens[1], g->lens[2], g->lens[3], g->lens[4], g->lens[5], g->lens[6], g->lens[7], g->lens[8]};
 }
 
-// the ray of every output pixel: computed when the (lens, width, height) of the cached map is another
-int rect_rays(rship_ctx* c, const rship_rectify_cfg* g) {
+// the ray of every output pixel: computed when the (lens, width, height) of the cached map is another.  The cache has two
+// places: the rectifier's and the stabiliser's map (and a colour call's luma map), and a 4:2:0 call's chroma map.
+int rect_rays_into(rship_ctx* c, const rship_rectify_cfg* g, DevBuf& rays, double* cached_key, bool& ok) {
     double key[10];
     for (int i = 0; i < 8; ++i) key[i] = g->lens[i + 1]; // (the readout time does not enter a ray)
     key[8] = g->width;
     key[9] = g->height;
-    if (c->rect_rays_ok && !memcmp(key, c->rect_key, sizeof(key))) return 0;
-    c->rect_rays_ok = false;
-    if (ensure(c, c->rect_rays, (size_t)g->width * g->height * sizeof(float4))) return 1;
-    RectRaysArgs A{rect_lens(g), g->width, g->height, (float4*)c->rect_rays.p};
+    if (ok && !memcmp(key, cached_key, sizeof(key))) return 0;
+    ok = false;
+    if (ensure(c, rays, (size_t)g->width * g->height * sizeof(float4))) return 1;
+    RectRaysArgs A{rect_lens(g), g->width, g->height, (float4*)rays.p};
     hipLaunchKernelGGL(rectify_rays_kernel, dim3((g->width + kRectTW - 1) / kRectTW, (g->height + kRectTH - 1) / kRectTH), dim3(256), 0,
                        c->stream, A);
     RS_HIP(hipGetLastError());
-    memcpy(c->rect_key, key, sizeof(key));
-    c->rect_rays_ok = true;
+    memcpy(cached_key, key, sizeof(key));
+    ok = true;
     return 0;
 }
+
+int rect_rays(rship_ctx* c, const rship_rectify_cfg* g) { return rect_rays_into(c, g, c->rect_rays, c->rect_key, c->rect_rays_ok); }
 
 RectRowsArgs rect_rows_args(rship_ctx* c, const rship_rectify_cfg* g) {
     RectRowsArgs R{};
@@ -3913,8 +3926,9 @@ int stab_check(rship_ctx* c, const rship_stabilize_cfg* g) {
     return 0;
 }
 
-// the ray map of the output camera with the lens's distortion: the rectifier's cache, keyed by that camera and the output's size
-int stab_rays(rship_ctx* c, const rship_stabilize_cfg* g) {
+// the ray map of the output camera with the lens's distortion: the rectifier's cache, keyed by that camera and the output's
+// size (chroma: the cache's second place)
+int stab_rays(rship_ctx* c, const rship_stabilize_cfg* g, bool chroma = false) {
     if (g->camera != 0) return 0;
     rship_rectify_cfg r{};
     r.width = g->out_width;
@@ -3922,7 +3936,7 @@ int stab_rays(rship_ctx* c, const rship_stabilize_cfg* g) {
     r.lens[0] = g->lens[0];
     for (int i = 0; i < 4; ++i) r.lens[1 + i] = g->cam[i];
     for (int i = 5; i < 9; ++i) r.lens[i] = g->lens[i];
-    return rect_rays(c, &r);
+    return chroma ? rect_rays_into(c, &r, c->rect_rays_c, c->rect_key_c, c->rect_rays_c_ok) : rect_rays(c, &r);
 }
 
 // the Gaussian weights of the path's taps, tabulated once in fp64 on the host
@@ -4174,6 +4188,260 @@ int rship_stabilize_coverage(rship_ctx* c, const double* frame_times, uint32_t n
         RS_HIP(hipGetLastError());
     }
     RS_HIP(hipMemcpyAsync(outside, c->stab_cover.p, counts, hipMemcpyDeviceToHost, c->stream));
+    return sync_stream(c);
+}
+
+} // extern "C"
+
+// ===========================================================================
+// colour frames (kernels/color.hpp; declared in color_hip.h, called by color_api.cpp).  The stabiliser's plumbing with
+// several planes per frame: one rows launch and one render launch per chunk.
+
+namespace {
+
+struct ColorPlane {
+    size_t row_bytes;
+    uint32_t rows;
+};
+
+// the planes of a width x height frame -> their number
+int color_planes(int format, uint32_t w, uint32_t h, ColorPlane* pl) {
+    switch (format) {
+    case 0: pl[0] = {w, h}; return 1;
+    case 1: pl[0] = {w, h}; pl[1] = {w, h / 2}; return 2;
+    case 2: pl[0] = {w, h}; pl[1] = pl[2] = {w / 2, h / 2}; return 3;
+    case 3: pl[0] = {(size_t)w * 4, h}; return 1;
+    }
+    return 0;
+}
+
+bool color_is_yuv(int format) { return format == 1 || format == 2; }
+
+int color_check(rship_ctx* c, const rship_color_cfg* g) {
+    if (!g || g->format < 0 || g->format > 3) return set_err(c, "color: bad configuration");
+    for (int k = 0; k < 4; ++k)
+        if (g->fill[k] < 0 || g->fill[k] > 255) return set_err(c, "color: bad configuration");
+    if (stab_check(c, &g->luma)) return 1;
+    if (color_is_yuv(g->format)) {
+        const rship_stabilize_cfg &l = g->luma, &k = g->chroma;
+        if (stab_check(c, &k)) return 1;
+        if ((l.width | l.height | l.out_width | l.out_height) & 1u || k.width != l.width / 2 || k.height != l.height / 2 ||
+            k.out_width != l.out_width / 2 || k.out_height != l.out_height / 2 || k.camera != l.camera || k.iterations != l.iterations ||
+            !std::isfinite(g->chroma_time))
+            return set_err(c, "color: bad configuration");
+    }
+    return 0;
+}
+
+// every plane of an image is host memory, or every plane memory of the context's device
+int color_kind(rship_ctx* c, const rship_color_image* img, int n_planes, const char* what, bool* on_device) {
+    for (int k = 0; k < n_planes; ++k) {
+        bool dev = false;
+        if (rect_pointer(c, img->plane[k], what, &dev, "color")) return 1;
+        if (k && dev != *on_device) return set_err(c, std::string("color: ") + what + " have planes of mixed kinds, host and device memory");
+        *on_device = dev;
+    }
+    return 0;
+}
+
+ColorCam color_cam(const rship_stabilize_cfg* g, const float4* rays) {
+    ColorCam C{};
+    C.rays = rays;
+    C.lens = stab_lens_f(g);
+    C.cam = rs::StabCamF{(float)g->cam[0], (float)g->cam[1], (float)g->cam[2], (float)g->cam[3]};
+    C.y_scale = (float)g->height / (float)g->out_height;
+    return C;
+}
+
+} // namespace
+
+extern "C" {
+
+int rship_color_frames(rship_ctx* c, const rship_color_image* in, uint32_t n_frames, const double* frame_times, const double* targets,
+                       const rship_color_cfg* cfg, const rship_color_image* out, uint64_t* n_outside, size_t budget_bytes) {
+    DeviceGuard dev_guard(c);
+    if (color_check(c, cfg)) return 1;
+    if (!in || !out || !frame_times) return set_err(c, "color: null pointer");
+    if (!n_frames) return 0;
+    rship_stabilize_cfg L = cfg->luma;
+    L.fill = cfg->fill[0];
+    const bool yuv = color_is_yuv(cfg->format);
+    const uint32_t h = L.height, ow = L.out_width, oh = L.out_height, hc = yuv ? h / 2 : 0;
+    ColorPlane pi[3] = {}, po[3] = {};
+    const int np = color_planes(cfg->format, L.width, h, pi);
+    color_planes(cfg->format, ow, oh, po);
+    size_t in_bytes = 0, out_bytes = 0;
+    for (int k = 0; k < np; ++k) {
+        if (!in->plane[k] || !out->plane[k]) return set_err(c, "color: null pointer");
+        if (in->pitch[k] < pi[k].row_bytes || out->pitch[k] < po[k].row_bytes ||
+            (n_frames > 1 && (in->stride[k] < in->pitch[k] * pi[k].rows || out->stride[k] < out->pitch[k] * po[k].rows)))
+            return set_err(c, "color: pitch or frame stride too small");
+        in_bytes += pi[k].row_bytes * pi[k].rows;
+        out_bytes += po[k].row_bytes * po[k].rows;
+    }
+    bool dev_in = false, dev_out = false;
+    if (color_kind(c, in, np, "the frames", &dev_in) || color_kind(c, out, np, "the stabilised frames", &dev_out)) return 1;
+    // a frame's bytes: both row tables and every plane that has to pass through the slot
+    const size_t tab = (size_t)(h + 1) * 9 * sizeof(float), tab_c = yuv ? (size_t)(hc + 1) * 9 * sizeof(float) : 0;
+    const size_t per_frame = tab + tab_c + (dev_in ? 0 : in_bytes) + (dev_out ? 0 : out_bytes);
+    const size_t budget = budget_bytes ? budget_bytes : kRectBudget;
+    const uint32_t chunk = (uint32_t)std::min<uint64_t>(std::min(n_frames, kRectMaxChunk), std::max<uint64_t>(1, budget / 2 / per_frame));
+    const size_t tab_bytes = ((size_t)chunk * tab + 255) / 256 * 256, tab_c_bytes = ((size_t)chunk * tab_c + 255) / 256 * 256;
+    const size_t slot_bytes = tab_bytes + tab_c_bytes + (size_t)chunk * (per_frame - tab - tab_c);
+    // where the chunk's planes lie in a slot: every plane packed, [chunk][rows][row bytes]
+    size_t off_in[3] = {}, off_out[3] = {}, off = tab_bytes + tab_c_bytes;
+    for (int k = 0; k < np && !dev_in; ++k) { off_in[k] = off; off += (size_t)chunk * pi[k].row_bytes * pi[k].rows; }
+    for (int k = 0; k < np && !dev_out; ++k) { off_out[k] = off; off += (size_t)chunk * po[k].row_bytes * po[k].rows; }
+    for (uint32_t s = 0; s < (n_frames > chunk ? 2u : 1u); ++s)
+        if (ensure(c, c->rect_slot[s], slot_bytes)) return 1;
+    if (ensure(c, c->rect_times, (size_t)n_frames * 16) || ensure(c, c->rect_count, (size_t)n_frames * 16) || rect_events(c)) return 1;
+    // the frames' times, then the chroma planes'; the filled pixels of plane 0, then the filled chroma samples
+    std::vector<double> times(2 * (size_t)n_frames);
+    for (uint32_t k = 0; k < n_frames; ++k) {
+        times[k] = frame_times[k];
+        times[n_frames + k] = frame_times[k] + cfg->chroma_time;
+    }
+    RS_HIP(hipMemcpy(c->rect_times.p, times.data(), times.size() * 8, hipMemcpyHostToDevice));
+    RS_HIP(hipMemsetAsync(c->rect_count.p, 0, (size_t)n_frames * 16, c->stream));
+    if (stab_fill_targets(c, &L, targets, n_frames) || stab_rays(c, &L) || (yuv && stab_rays(c, &cfg->chroma, true))) return 1;
+    ColorRowsArgs R{};
+    R.table = (const double*)c->coef64.p;
+    R.start = L.start;
+    R.fs = L.fs;
+    R.ro = L.lens[0];
+    R.delay = L.delay;
+    R.n_knots = c->n_knots;
+    R.rows = h;
+    R.rows_c = hc;
+    StabArgs G = stab_args(c, &L); // GRAY8: the stabiliser's kernel
+    ColorArgs A{};
+    A.luma = color_cam(&L, (const float4*)c->rect_rays.p);
+    if (yuv) A.chroma = color_cam(&cfg->chroma, (const float4*)c->rect_rays_c.p);
+    A.width = L.width;
+    A.height = h;
+    A.out_width = ow;
+    A.out_height = oh;
+    A.iterations = L.iterations;
+    A.fill = (uint32_t)cfg->fill[0] | (uint32_t)cfg->fill[1] << 8 | (uint32_t)cfg->fill[2] << 16 | (uint32_t)cfg->fill[3] << 24;
+    // the chunk pipeline of rship_rectify_frames: chunk j in slot j & 1, uploads and downloads on the copy stream
+    auto upload = [&](int slot, bool reused, uint32_t f0, uint32_t cnt) -> int {
+        if (reused) RS_HIP(hipStreamWaitEvent(c->copy_stream, c->trk_k[slot], 0));
+        for (int k = 0; k < np && !dev_in; ++k)
+            if (rect_copy(c, (uint8_t*)c->rect_slot[slot].p + off_in[k], pi[k].row_bytes, pi[k].row_bytes * pi[k].rows,
+                          in->plane[k] + (size_t)f0 * in->stride[k], in->pitch[k], in->stride[k], (uint32_t)pi[k].row_bytes, pi[k].rows, cnt))
+                return 1;
+        RS_HIP(hipEventRecord(c->trk_up[slot], c->copy_stream));
+        return 0;
+    };
+    bool used[2] = {false, false};
+    int slot = 0;
+    if (upload(0, false, 0, std::min(chunk, n_frames))) return 1;
+    for (uint32_t f0 = 0; f0 < n_frames;) {
+        const uint32_t cnt = std::min(chunk, n_frames - f0);
+        uint8_t* base = (uint8_t*)c->rect_slot[slot].p;
+        RS_HIP(hipStreamWaitEvent(c->stream, c->trk_up[slot], 0));
+        R.times = (const double*)c->rect_times.p + f0;
+        R.times_c = (const double*)c->rect_times.p + n_frames + f0;
+        R.targets = (const double*)c->stab_targets.p + (size_t)f0 * 4;
+        R.rows_tab = (float*)base;
+        R.rows_tab_c = (float*)(base + tab_bytes);
+        R.n_frames = cnt;
+        hipLaunchKernelGGL(color_rows_kernel, dim3((h + 1 + (yuv ? hc + 1 : 0) + 255) / 256, cnt), dim3(256), 0, c->stream, R);
+        RS_HIP(hipGetLastError());
+        A.luma.rows_tab = (const float*)base;
+        A.chroma.rows_tab = (const float*)(base + tab_bytes);
+        A.outside = (unsigned long long*)c->rect_count.p + f0;
+        A.outside_c = (unsigned long long*)c->rect_count.p + n_frames + f0;
+        for (int k = 0; k < np; ++k) {
+            if (dev_in) { A.src[k] = in->plane[k] + (size_t)f0 * in->stride[k]; A.src_pitch[k] = in->pitch[k]; A.src_stride[k] = in->stride[k]; }
+            else { A.src[k] = base + off_in[k]; A.src_pitch[k] = pi[k].row_bytes; A.src_stride[k] = pi[k].row_bytes * pi[k].rows; }
+            if (dev_out) { A.dst[k] = out->plane[k] + (size_t)f0 * out->stride[k]; A.dst_pitch[k] = out->pitch[k]; A.dst_stride[k] = out->stride[k]; }
+            else { A.dst[k] = base + off_out[k]; A.dst_pitch[k] = po[k].row_bytes; A.dst_stride[k] = po[k].row_bytes * po[k].rows; }
+        }
+        const dim3 grid((ow + kRectTW - 1) / kRectTW, (oh + kRectTH - 1) / kRectTH, cnt);
+        const dim3 grid_c((ow / 2 + kRectTW - 1) / kRectTW, (oh / 2 + kRectTH - 1) / kRectTH, cnt);
+        const bool lens_cam = L.camera == 0;
+        switch (cfg->format) {
+        case 0:
+            G.rows_tab = A.luma.rows_tab;
+            G.outside = A.outside;
+            G.src = A.src[0]; G.src_pitch = A.src_pitch[0]; G.src_stride = A.src_stride[0];
+            G.dst = A.dst[0]; G.dst_pitch = A.dst_pitch[0]; G.dst_stride = A.dst_stride[0];
+            stab_launch<false>(c, &L, G, cnt);
+            break;
+        case 1:
+            if (lens_cam) hipLaunchKernelGGL((color_yuv_kernel<0, true>), grid_c, dim3(256), 0, c->stream, A);
+            else hipLaunchKernelGGL((color_yuv_kernel<1, true>), grid_c, dim3(256), 0, c->stream, A);
+            break;
+        case 2:
+            if (lens_cam) hipLaunchKernelGGL((color_yuv_kernel<0, false>), grid_c, dim3(256), 0, c->stream, A);
+            else hipLaunchKernelGGL((color_yuv_kernel<1, false>), grid_c, dim3(256), 0, c->stream, A);
+            break;
+        default:
+            if (lens_cam) hipLaunchKernelGGL((color_rgba_kernel<0>), grid, dim3(256), 0, c->stream, A);
+            else hipLaunchKernelGGL((color_rgba_kernel<1>), grid, dim3(256), 0, c->stream, A);
+        }
+        RS_HIP(hipGetLastError());
+        RS_HIP(hipEventRecord(c->trk_k[slot], c->stream));
+        used[slot] = true;
+        const uint32_t next = f0 + cnt;
+        if (next < n_frames && upload(slot ^ 1, used[slot ^ 1], next, std::min(chunk, n_frames - next))) return 1;
+        if (!dev_out) {
+            RS_HIP(hipStreamWaitEvent(c->copy_stream, c->trk_k[slot], 0));
+            for (int k = 0; k < np; ++k)
+                if (rect_copy(c, out->plane[k] + (size_t)f0 * out->stride[k], out->pitch[k], out->stride[k], base + off_out[k], po[k].row_bytes,
+                              po[k].row_bytes * po[k].rows, (uint32_t)po[k].row_bytes, po[k].rows, cnt))
+                    return 1;
+        }
+        f0 = next;
+        slot ^= 1;
+    }
+    std::vector<uint64_t> counts(n_outside ? 2 * (size_t)n_frames : 0);
+    if (n_outside) RS_HIP(hipMemcpyAsync(counts.data(), c->rect_count.p, counts.size() * 8, hipMemcpyDeviceToHost, c->stream));
+    RS_HIP(hipStreamSynchronize(c->copy_stream));
+    if (sync_stream(c)) return 1;
+    for (size_t k = 0; k < counts.size() / 2; ++k) {
+        n_outside[2 * k] = counts[k];
+        n_outside[2 * k + 1] = counts[n_frames + k];
+    }
+    return 0;
+}
+
+int rship_color_map(rship_ctx* c, int plane, double frame_time, const double* target, const rship_color_cfg* cfg, float* map_xy) {
+    {
+        DeviceGuard dev_guard(c);
+        if (color_check(c, cfg)) return 1;
+        if (plane != 0 && !(plane == 1 && color_is_yuv(cfg->format))) return set_err(c, "color: the format has no such plane");
+    }
+    if (plane == 0) return rship_stabilize_map(c, frame_time, target, &cfg->luma, map_xy);
+    // the chroma plane: the stabiliser's map of the chroma camera at the chroma frame time, against the FRAME's target
+    DeviceGuard dev_guard(c);
+    if (!map_xy) return set_err(c, "color: null pointer");
+    bool on_dev = false;
+    if (rect_pointer(c, map_xy, "the map", &on_dev, "color")) return 1;
+    const rship_stabilize_cfg* g = &cfg->chroma;
+    const uint32_t h = g->height;
+    const size_t n = (size_t)g->out_width * g->out_height;
+    if (ensure(c, c->rect_slot[0], (size_t)(h + 1) * 9 * sizeof(float)) || ensure(c, c->rect_times, 16) ||
+        (!on_dev && ensure(c, c->rect_tmp, n * sizeof(float2))))
+        return 1;
+    const double times[2] = {frame_time, frame_time + cfg->chroma_time};
+    RS_HIP(hipMemcpy(c->rect_times.p, times, 16, hipMemcpyHostToDevice));
+    if (stab_fill_targets(c, &cfg->luma, target, 1) || stab_rays(c, g, true)) return 1;
+    StabRowsArgs R = stab_rows_args(c, g);
+    R.times = (const double*)c->rect_times.p + 1;
+    R.targets = (const double*)c->stab_targets.p;
+    R.rows_tab = (float*)c->rect_slot[0].p;
+    R.n_frames = 1;
+    hipLaunchKernelGGL(stabilize_rows_kernel, dim3((h + 1 + 255) / 256, 1), dim3(256), 0, c->stream, R);
+    RS_HIP(hipGetLastError());
+    StabArgs A = stab_args(c, g);
+    A.rays = (const float4*)c->rect_rays_c.p;
+    A.rows_tab = (const float*)c->rect_slot[0].p;
+    A.map = on_dev ? (float2*)map_xy : (float2*)c->rect_tmp.p;
+    stab_launch<true>(c, g, A, 1);
+    RS_HIP(hipGetLastError());
+    if (!on_dev) RS_HIP(hipMemcpyAsync(map_xy, c->rect_tmp.p, n * sizeof(float2), hipMemcpyDeviceToHost, c->stream));
     return sync_stream(c);
 }
 

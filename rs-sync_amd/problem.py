@@ -714,6 +714,21 @@ class SyncProblem:
         from . import stabilize
         return stabilize.stabilize_zoom(self, width, height, lens, frame_times, delay, zooms, **params)
 
+    def stabilize_color(self, fmt, frames, frame_times, lens, delay, **params):
+        """Colour frames (rssync_amd.color: GRAY8, NV12, I420, RGBA32) rendered at the smoothed path's orientations, or at
+        `targets`, all planes of a frame in one pass (include/rssync_color.h) -> (frames in the layout of `frames`,
+        n_outside (n, 2)).  params: targets, out_size, out, chroma_site, fills, sigma, zoom, camera, out_camera,
+        iterations, fill."""
+        from . import color
+        return color.stabilize_color(self, fmt, frames, frame_times, lens, delay, **params)
+
+    def color_map(self, fmt, plane, width, height, lens, frame_time, delay, **params):
+        """-> float32 (rows, cols, 2): where stabilize_color looks every output sample of `plane` up (plane 1: the chroma
+        plane of NV12 and I420, in its own coordinates).  params: target, out_size, chroma_site, sigma, zoom, camera,
+        out_camera, iterations."""
+        from . import color
+        return color.color_map(self, fmt, plane, width, height, lens, frame_time, delay, **params)
+
     def device_context(self):
         """rship_ctx* of this problem (include/rssync_hip.h), for kernel-level tools."""
         return self._lib.rssync_ext_device_context(self._h)

@@ -65,15 +65,18 @@ def _shade(P, tex, weight=None):
 
 
 def render(gyro, frame_begin, frame_end, lens=synth.LENS, rows=synth.IMAGE_ROWS, cols=synth.IMAGE_COLS, seed=0,
-           d_true=synth.D_TRUE, flat=None):
+           d_true=synth.D_TRUE, flat=None, texture_seed=None):
     """-> frames (n, rows, cols) uint8, frame_times (n,) s, for frames [frame_begin, frame_end).
+
+    texture_seed: None = `seed`; else the walls carry that seed's texture while the camera still moves along `seed`'s
+    path: another plane (the U or V of a colour frame) of the same shot.
 
     flat: None, or a world-space box ((x0, y0, z0), (x1, y1, z1)) whose part of the walls is rendered as constant gray
     FLAT_GRAY (sky, a blank wall), the texture fading in over FLAT_EDGE m around it.  Then a third result,
     mask (n, rows, cols) bool: the pixels that see the region."""
     ys, xs = np.mgrid[0:rows, 0:cols]
     rays = synth.unproject(np.stack([xs, ys], axis=-1).astype(np.float64), lens)   # (rows, cols, 3), once per lens
-    tex = _texture(seed)
+    tex = _texture(seed if texture_seed is None else texture_seed)
     ro = lens[0]
     n = frame_end - frame_begin
     out = np.empty((n, rows, cols), np.uint8)
