@@ -1,4 +1,5 @@
-"""Colour frames stabilised on the GPU: NV12, I420 and RGBA32 (include/rssync_color.h).
+"""Colour frames stabilised on the GPU: NV12, I420 and RGBA32 (include/rssync_color.h), and their 10- and 16-bit kin GRAY16,
+P010, P016 and I010 (include/rssync_color16.h).
 
 What ``stabilize_frames`` does for 8-bit grayscale, for the layouts decoders hand out and viewers take, every plane of a
 frame rendered in one pass (csrc/kernels/color.hpp).  The luma plane (and every channel of RGBA) is the stabiliser's result
@@ -11,6 +12,10 @@ position (2 cu + ox, 2 cv + oy) -- ``chroma_site`` CHROMA_CENTER (0.5, 0.5) or C
     NV12     (Y (n, H, W), UV (n, H/2, W/2, 2))
     I420     (Y (n, H, W), U (n, H/2, W/2), V (n, H/2, W/2))
     RGBA32   (n, H, W, 4)
+
+The 16-bit formats have their sibling's shapes -- GRAY16 GRAY8's, P010 and P016 NV12's, I010 I420's -- with uint16 samples:
+numpy uint16 arrays, or torch.uint16 / torch.int16 tensors on the problem's device (the bits are taken as unsigned).  P010
+keeps a sample's ten bits in the high end of the word (value << 6); I010's words are the values.
 
 The result is of the same kind and layout with the output's size, or written into ``out``.
 
@@ -29,9 +34,12 @@ _SZ = C.c_size_t
 _PU64 = C.POINTER(C.c_uint64)
 
 GRAY8, NV12, I420, RGBA32 = 0, 1, 2, 3
+GRAY16, P010, P016, I010 = 16, 17, 18, 19
+SIBLING = {GRAY16: GRAY8, P010: NV12, P016: NV12, I010: I420}     # the 8-bit format with the same planes and geometry
+DEPTH = {GRAY16: 16, P010: 10, P016: 16, I010: 10}               # bits of a sample value
 CHROMA_CENTER, CHROMA_LEFT = 0, 1
 CHROMA_OFFSET = {CHROMA_CENTER: (0.5, 0.5), CHROMA_LEFT: (0.0, 0.5)}
-_N_PLANES = {GRAY8: 1, NV12: 2, I420: 3, RGBA32: 1}
+_N_PLANES = {GRAY8: 1, NV12: 2, I420: 3, RGBA32: 1, GRAY16: 1, P010: 2, P016: 2, I010: 3}
 
 
 class ColorImage(C.Structure):
@@ -52,10 +60,13 @@ class _Cfg(C.Structure):
 _PI = C.POINTER(ColorImage)
 _PP = C.POINTER(ColorParams)
 
-# name -> (restype, argtypes): every function include/rssync_color.h declares, and the internal launcher the tests call
+# name -> (restype, argtypes): every function include/rssync_color.h and include/rssync_color16.h declare, and the internal
+# launcher the tests call
 SIGNATURES = {
     "rssync_color_stabilize": (C.c_int, [C.c_void_p, C.c_int, _PI, _SZ, _SZ, _SZ, _PD, C.c_void_p, C.c_double, _PD, _PP, _PI, _SZ, _SZ,
                                          _PU64]),
+    "rssync_color16_stabilize": (C.c_int, [C.c_void_p, C.c_int, _PI, _SZ, _SZ, _SZ, _PD, C.c_void_p, C.c_double, _PD, _PP, _PI, _SZ, _SZ,
+                                           _PU64]),
     "rssync_color_map": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _SZ, _SZ, C.c_void_p, _SZ, _SZ, C.c_double, C.c_double, _PD, _PP,
                                    C.c_void_p]),
     "rship_color_frames": (C.c_int, [C.c_void_p, _PI, C.c_uint32, _PD, _PD, C.POINTER(_Cfg), _PI, _PU64, _SZ]),
@@ -86,7 +97,8 @@ def _lib_of(problem):
 
 
 def params(chroma_site=CHROMA_CENTER, fills=None, **kw):
-    """fills: None = the defaults from `fill` (U, V = 128, A = 255), else the values in the format's order; kw: the
+    """fills: None = the defaults from `fill` (U, V = 128, A = 255; 16-bit formats: `fill` << (depth - 8) and
+    1 << (depth - 1)), else the values in the format's order, 16-bit formats: in sample values; kw: the
     stabiliser's sigma, zoom, camera, out_camera, iterations, fill.  Everything is handed on as written."""
     prm = ColorParams()
     prm.stab = _stab_params(**kw)
@@ -99,28 +111,30 @@ def params(chroma_site=CHROMA_CENTER, fills=None, **kw):
 
 
 def plane_shapes(fmt, n, h, w):
-    """the shapes of a format's planes for n frames of w x h"""
+    """the shapes of a format's planes for n frames of w x h (a 16-bit format's are its sibling's)"""
+    fmt = SIBLING.get(fmt, fmt)
     return {GRAY8: [(n, h, w)], NV12: [(n, h, w), (n, h // 2, w // 2, 2)], I420: [(n, h, w), (n, h // 2, w // 2), (n, h // 2, w // 2)],
             RGBA32: [(n, h, w, 4)]}[fmt]
 
 
 def _as_planes(fmt, frames):
     if fmt not in _N_PLANES:
-        raise ValueError("format must be GRAY8, NV12, I420 or RGBA32")
+        raise ValueError("format must be GRAY8, NV12, I420, RGBA32, GRAY16, P010, P016 or I010")
     planes = [frames] if _N_PLANES[fmt] == 1 else list(frames)
     if len(planes) != _N_PLANES[fmt]:
         raise ValueError("this format has %d planes" % _N_PLANES[fmt])
     return planes
 
 
-def _rows(a, writable):
-    """one plane -> (pointer, pitch, frame stride, keep-alive): the bytes of a row (its last one or two axes) must be
-    contiguous; an input that is laid out otherwise is copied, an output is refused"""
+def _rows(a, writable, size=1):
+    """one plane of `size`-byte samples -> (pointer, pitch, frame stride in bytes, keep-alive): the bytes of a row (its last
+    one or two axes) must be contiguous; an input that is laid out otherwise is copied, an output is refused"""
     inner = a.ndim - 2                          # axes that make up a row: 1, or 2 for (W/2, 2) and (W, 4)
+    name = "uint8" if size == 1 else "uint16"
     if _is_torch(a) and a.is_cuda:
         import torch
-        if a.dtype != torch.uint8:
-            raise ValueError("planes must be uint8")
+        if a.dtype not in ((torch.uint8,) if size == 1 else (torch.uint16, torch.int16)):
+            raise ValueError("planes must be %s%s" % (name, "" if size == 1 else " (or int16: the bits are taken as unsigned)"))
         st, row = a.stride(), int(np.prod(a.shape[2:]))
         ok = st[-1] == 1 and (inner == 1 or st[-2] == a.shape[-1]) and st[1] >= row and (a.shape[0] < 2 or st[0] >= st[1] * a.shape[1])
         if not ok:
@@ -129,14 +143,14 @@ def _rows(a, writable):
             a = a.contiguous()
             st = a.stride()
         torch.cuda.current_stream(a.device).synchronize()
-        return a.data_ptr(), st[1], st[0], a
+        return a.data_ptr(), st[1] * size, st[0] * size, a
     a = a.numpy() if _is_torch(a) else np.asarray(a)
-    if a.dtype != np.uint8:
-        raise ValueError("planes must be uint8")
-    st, row = a.strides, int(np.prod(a.shape[2:]))
-    ok = st[-1] == 1 and (inner == 1 or st[-2] == a.shape[-1]) and st[1] >= row and (a.shape[0] < 2 or st[0] >= st[1] * a.shape[1])
+    if a.dtype != (np.uint8 if size == 1 else np.uint16):
+        raise ValueError("planes must be %s" % name)
+    st, row = a.strides, int(np.prod(a.shape[2:])) * size
+    ok = st[-1] == size and (inner == 1 or st[-2] == a.shape[-1] * size) and st[1] >= row and (a.shape[0] < 2 or st[0] >= st[1] * a.shape[1])
     if writable and not (ok and a.flags.writeable):
-        raise ValueError("out planes must be writable uint8 arrays with contiguous rows")
+        raise ValueError("out planes must be writable %s arrays with contiguous rows" % name)
     if not ok:
         a = np.ascontiguousarray(a)
         st = a.strides
@@ -150,7 +164,7 @@ def _image(fmt, planes, n, h, w, writable):
     for k, (a, shape) in enumerate(zip(planes, shapes)):
         if tuple(a.shape) != shape:
             raise ValueError("plane %d must have the shape %s, not %s" % (k, shape, tuple(a.shape)))
-        img.plane[k], img.pitch[k], img.stride[k], alive = _rows(a, writable)
+        img.plane[k], img.pitch[k], img.stride[k], alive = _rows(a, writable, 2 if fmt in SIBLING else 1)
         keep.append(alive)
     return img, keep
 
@@ -166,8 +180,8 @@ def _out_like(fmt, planes, n, oh, ow):
     y = planes[0]
     if _is_torch(y) and y.is_cuda:
         import torch
-        return [torch.empty(s, dtype=torch.uint8, device=y.device) for s in plane_shapes(fmt, n, oh, ow)]
-    return [np.empty(s, np.uint8) for s in plane_shapes(fmt, n, oh, ow)]
+        return [torch.empty(s, dtype=torch.uint16 if fmt in SIBLING else torch.uint8, device=y.device) for s in plane_shapes(fmt, n, oh, ow)]
+    return [np.empty(s, np.uint16 if fmt in SIBLING else np.uint8) for s in plane_shapes(fmt, n, oh, ow)]
 
 
 def stabilize_color(problem, fmt, frames, frame_times, lens, delay, targets=None, out_size=None, out=None, chroma_site=CHROMA_CENTER,
@@ -187,8 +201,9 @@ def stabilize_color(problem, fmt, frames, frame_times, lens, delay, targets=None
     prm = params(chroma_site, fills, **kw)
     tptr, tkeep = _targets(targets, n)
     outside = np.zeros((max(n, 1), 2), np.uint64)
-    _check(problem, lib.rssync_color_stabilize(problem._h, int(fmt), C.byref(src), n, w, h, t.ctypes.data_as(_PD), L.ctypes.data,
-                                               float(delay), tptr, C.byref(prm), C.byref(dst), ow, oh, outside.ctypes.data_as(_PU64)))
+    entry = lib.rssync_color16_stabilize if fmt in SIBLING else lib.rssync_color_stabilize
+    _check(problem, entry(problem._h, int(fmt), C.byref(src), n, w, h, t.ctypes.data_as(_PD), L.ctypes.data, float(delay), tptr, C.byref(prm),
+                           C.byref(dst), ow, oh, outside.ctypes.data_as(_PU64)))
     del keep, okeep, tkeep
     if out is not None:
         return out, outside[:n]
@@ -237,7 +252,7 @@ def stabilize_color_budget(problem, fmt, frames, frame_times, lens, delay, budge
     numpy frames -> (planes, n_outside (n, 2))"""
     lib = _lib_of(problem)
     if fills is None:
-        fills = (0, 0, 0, 255) if fmt == RGBA32 else (0, 128, 128, 0)
+        fills = (0, 0, 0, 255) if fmt == RGBA32 else (0, 128 << (DEPTH.get(fmt, 8) - 8), 128 << (DEPTH.get(fmt, 8) - 8), 0)
     planes = _as_planes(fmt, frames)
     n, h, w = _size(fmt, planes)
     src, keep = _image(fmt, planes, n, h, w, False)
@@ -250,18 +265,18 @@ def stabilize_color_budget(problem, fmt, frames, frame_times, lens, delay, budge
 
     def stab_cfg(w_, h_, ow_, oh_, lens_, cam_):
         return _StabCfg(w_, h_, ow_, oh_, (C.c_double * 9)(*lens_), (C.c_double * 4)(*cam_), start, fs, n_knots, float(delay), float(sigma),
-                        CAMERA_LENS, int(iterations), int(fills[0]))
+                        CAMERA_LENS, int(iterations), 0 if fmt in SIBLING else int(fills[0]))   # (16-bit: cfg.fill alone is read)
 
     cfg = _Cfg()
     cfg.luma = stab_cfg(w, h, ow, oh, L, cam)
     cfg.chroma = cfg.luma
-    if fmt in (NV12, I420):
+    if SIBLING.get(fmt, fmt) in (NV12, I420):
         lens_c, cam_c, cfg.chroma_time = chroma_config(L, w, h, ow, oh, chroma_site)
         cfg.chroma = stab_cfg(w // 2, h // 2, ow // 2, oh // 2, lens_c, cam_c)
     cfg.format = int(fmt)
     for k in range(4):
         cfg.fill[k] = int(fills[k])
-    res = [np.empty(s, np.uint8) for s in plane_shapes(fmt, n, oh, ow)]
+    res = [np.empty(s, np.uint16 if fmt in SIBLING else np.uint8) for s in plane_shapes(fmt, n, oh, ow)]
     dst, okeep = _image(fmt, res, n, oh, ow, True)
     outside = np.zeros((max(n, 1), 2), np.uint64)
     ctx = C.c_void_p(problem.device_context())

@@ -1,9 +1,11 @@
-// color_api.cpp -- the public colour entry points (include/rssync_color.h): the stabiliser's checks and defaults
+// color_api.cpp -- the public colour entry points (include/rssync_color.h, and include/rssync_color16.h for samples in
+// 16-bit containers, which differ in the sample alone): the stabiliser's checks and defaults
 // (stabilize_host.hpp), the fills, the chroma plane's lens, frame time and output camera (color_math.hpp), the planes'
 // pitches, strides and overlaps.  The work runs in rship_color_* (color_hip.h).
 //
 // A file of its own, linked into the product library only, like stabilize_api.cpp.
 #include "../../include/rssync_color.h"
+#include "../../include/rssync_color16.h"
 #include "color_hip.h"
 #include "color_math.hpp"
 #include "stabilize_host.hpp"
@@ -18,26 +20,46 @@ using namespace rssync_stab_host;
 
 namespace {
 
-bool is_yuv(int format) { return format == RSSYNC_COLOR_NV12 || format == RSSYNC_COLOR_I420; }
+bool is_16(int format) { return format >= RSSYNC_COLOR16_GRAY16 && format <= RSSYNC_COLOR16_I010; }
+
+// the 8-bit format whose planes and geometry a 16-bit format has
+int sibling(int format) {
+    switch (format) {
+    case RSSYNC_COLOR16_GRAY16: return RSSYNC_COLOR_GRAY8;
+    case RSSYNC_COLOR16_P010:
+    case RSSYNC_COLOR16_P016: return RSSYNC_COLOR_NV12;
+    case RSSYNC_COLOR16_I010: return RSSYNC_COLOR_I420;
+    default: return format;
+    }
+}
+
+// bits of a sample value
+int depth(int format) { return !is_16(format) ? 8 : (format == RSSYNC_COLOR16_P010 || format == RSSYNC_COLOR16_I010) ? 10 : 16; }
+
+bool is_yuv(int format) { return sibling(format) == RSSYNC_COLOR_NV12 || sibling(format) == RSSYNC_COLOR_I420; }
 
 struct Plane {
     size_t row_bytes, rows;
 };
 
-// the planes of a width x height frame -> their number
+// the planes of a width x height frame -> their number; a 16-bit format's rows are twice its sibling's bytes
 int planes_of(int format, size_t w, size_t h, Plane* pl) {
-    switch (format) {
-    case RSSYNC_COLOR_GRAY8: pl[0] = {w, h}; return 1;
-    case RSSYNC_COLOR_NV12: pl[0] = {w, h}; pl[1] = {w, h / 2}; return 2;
-    case RSSYNC_COLOR_I420: pl[0] = {w, h}; pl[1] = pl[2] = {w / 2, h / 2}; return 3;
+    const size_t b = is_16(format) ? 2 : 1;
+    switch (sibling(format)) {
+    case RSSYNC_COLOR_GRAY8: pl[0] = {b * w, h}; return 1;
+    case RSSYNC_COLOR_NV12: pl[0] = {b * w, h}; pl[1] = {b * w, h / 2}; return 2;
+    case RSSYNC_COLOR_I420: pl[0] = {b * w, h}; pl[1] = pl[2] = {b * (w / 2), h / 2}; return 3;
     default: pl[0] = {4 * w, h}; return 1;
     }
 }
 
-// format, sizes, parameters -> the configuration of both cameras
+// format, sizes, parameters -> the configuration of both cameras.  wide: the call came through rssync_color16.h, whose
+// formats are the only ones it takes (and which the 8-bit entry points do not take)
 rship_color_cfg resolve_color(rssync_problem* p, int format, size_t width, size_t height, const rssync_lens* lens, size_t out_width,
-                              size_t out_height, double delay, const rssync_color_params* params) {
-    if (format < RSSYNC_COLOR_GRAY8 || format > RSSYNC_COLOR_RGBA32) panic("color: format must be one of RSSYNC_COLOR_*");
+                              size_t out_height, double delay, const rssync_color_params* params, bool wide = false) {
+    if (wide && !is_16(format)) panic("color: format must be one of RSSYNC_COLOR16_*");
+    if (!wide && (format < RSSYNC_COLOR_GRAY8 || format > RSSYNC_COLOR_RGBA32)) panic("color: format must be one of RSSYNC_COLOR_*");
+    const int bits = depth(format), top = (1 << bits) - 1;
     rssync_color_params q = params ? *params : rssync_color_params{};
     if (q.chroma_site != RSSYNC_CHROMA_CENTER && q.chroma_site != RSSYNC_CHROMA_LEFT)
         panic("color: chroma_site must be RSSYNC_CHROMA_CENTER or RSSYNC_CHROMA_LEFT");
@@ -45,7 +67,7 @@ rship_color_cfg resolve_color(rssync_problem* p, int format, size_t width, size_
     c.format = format;
     if (q.fill_set) {
         for (int k = 0; k < 4; ++k) {
-            if (q.fill[k] < 0 || q.fill[k] > 255) panic("color: fill " + std::to_string(k) + " must be 0 .. 255");
+            if (q.fill[k] < 0 || q.fill[k] > top) panic("color: fill " + std::to_string(k) + " must be 0 .. " + std::to_string(top));
             c.fill[k] = q.fill[k];
         }
         q.stab.fill = 0; // (not read)
@@ -60,9 +82,9 @@ rship_color_cfg resolve_color(rssync_problem* p, int format, size_t width, size_
     if (!q.fill_set) {
         const int f = c.luma.fill;
         const int by_format[4][4] = {{f, 0, 0, 0}, {f, 128, 128, 0}, {f, 128, 128, 0}, {f, f, f, 255}};
-        for (int k = 0; k < 4; ++k) c.fill[k] = by_format[format][k];
+        for (int k = 0; k < 4; ++k) c.fill[k] = by_format[sibling(format)][k] << (bits - 8);
     }
-    c.luma.fill = c.fill[0];
+    c.luma.fill = wide ? 0 : c.fill[0]; // (a 16-bit fill goes to the kernels from fill[] alone)
     c.chroma = c.luma;
     if (is_yuv(format)) {
         double ox, oy;
@@ -91,6 +113,8 @@ std::vector<Extent> check_image(const rssync_color_image* img, int format, size_
     for (int k = 0; k < np; ++k) {
         const std::string name = std::string(what) + " plane " + std::to_string(k);
         if (!img->plane[k]) panic("color: " + name + " is NULL");
+        if (is_16(format) && (((uintptr_t)img->plane[k] | img->pitch[k]) & 1 || (n_frames > 1 && (img->stride[k] & 1))))
+            panic("color: alignment: pointer, pitch and frame stride of " + name + " must be multiples of 2");
         if (img->pitch[k] < pl[k].row_bytes)
             panic("color: pitch " + std::to_string(img->pitch[k]) + " of " + name + " < its row of " + std::to_string(pl[k].row_bytes) + " bytes");
         if (n_frames > 1 && img->stride[k] < img->pitch[k] * pl[k].rows) panic("color: frame stride of " + name + " smaller than pitch * rows");
@@ -110,18 +134,14 @@ rship_color_image image_of(const rssync_color_image* img) {
     return r;
 }
 
-} // namespace
-
-extern "C" {
-
-int rssync_color_stabilize(rssync_problem* p, int format, const rssync_color_image* in, size_t n_frames, size_t width, size_t height,
-                           const double* frame_times, const rssync_lens* lens, double delay, const double* targets,
-                           const rssync_color_params* params, const rssync_color_image* out, size_t out_width, size_t out_height,
-                           uint64_t* n_outside) {
+// both stabilise entry points: they differ in the formats they take
+int stabilize_any(bool wide, rssync_problem* p, int format, const rssync_color_image* in, size_t n_frames, size_t width, size_t height,
+                  const double* frame_times, const rssync_lens* lens, double delay, const double* targets, const rssync_color_params* params,
+                  const rssync_color_image* out, size_t out_width, size_t out_height, uint64_t* n_outside) {
     return guarded([&] {
         if (!frame_times) panic("color: no frame times");
         if (n_frames > 0xffffffffu) panic("color: too many frames");
-        const rship_color_cfg cfg = resolve_color(p, format, width, height, lens, out_width, out_height, delay, params);
+        const rship_color_cfg cfg = resolve_color(p, format, width, height, lens, out_width, out_height, delay, params, wide);
         const std::vector<Extent> a = check_image(in, format, width, height, n_frames, "frames"),
                                   b = check_image(out, format, out_width, out_height, n_frames, "out");
         if (!n_frames) return;
@@ -136,6 +156,26 @@ int rssync_color_stabilize(rssync_problem* p, int format, const rssync_color_ima
         if (rship_color_frames(c, &di, (uint32_t)n_frames, frame_times, targets ? unit.data() : nullptr, &cfg, &dout, n_outside, 0))
             panic(std::string("hip: color: ") + rship_last_error(c));
     });
+}
+
+} // namespace
+
+extern "C" {
+
+int rssync_color_stabilize(rssync_problem* p, int format, const rssync_color_image* in, size_t n_frames, size_t width, size_t height,
+                           const double* frame_times, const rssync_lens* lens, double delay, const double* targets,
+                           const rssync_color_params* params, const rssync_color_image* out, size_t out_width, size_t out_height,
+                           uint64_t* n_outside) {
+    return stabilize_any(false, p, format, in, n_frames, width, height, frame_times, lens, delay, targets, params, out, out_width, out_height,
+                         n_outside);
+}
+
+int rssync_color16_stabilize(rssync_problem* p, int format, const rssync_color_image* in, size_t n_frames, size_t width, size_t height,
+                             const double* frame_times, const rssync_lens* lens, double delay, const double* targets,
+                             const rssync_color_params* params, const rssync_color_image* out, size_t out_width, size_t out_height,
+                             uint64_t* n_outside) {
+    return stabilize_any(true, p, format, in, n_frames, width, height, frame_times, lens, delay, targets, params, out, out_width, out_height,
+                         n_outside);
 }
 
 int rssync_color_map(rssync_problem* p, int format, int plane, size_t width, size_t height, const rssync_lens* lens, size_t out_width,

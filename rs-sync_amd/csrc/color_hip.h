@@ -1,5 +1,6 @@
 /*
- * color_hip.h -- the colour front's launchers in rssync_kernels.hip (kernels/color.hpp), called by color_api.cpp.
+ * color_hip.h -- the colour front's launchers in rssync_kernels.hip (kernels/color.hpp, kernels/color16.hpp), called by
+ * color_api.cpp.
  * Internal to librssync_core.so and not in include/rssync_hip.h, for stabilize_hip.h's reason: only the product library
  * links color_api.cpp.
  */
@@ -15,7 +16,7 @@
 extern "C" {
 #endif
 
-/* include/rssync_color.h's rssync_color_image */
+/* include/rssync_color.h's rssync_color_image; 16-bit formats: pointers, pitches and strides are multiples of 2 */
 typedef struct rship_color_image {
     uint8_t* plane[3];
     size_t pitch[3];
@@ -27,8 +28,9 @@ typedef struct rship_color_cfg {
     rship_stabilize_cfg luma;   /* plane 0, or the only plane: the stabiliser's configuration of the call (fill unused) */
     rship_stabilize_cfg chroma; /* 4:2:0: the chroma plane's size, lens and output camera; everything else as in luma */
     double chroma_time;         /* 4:2:0: ro * (oy / height), what a chroma plane's frame time lies after the frame's */
-    int32_t format;             /* RSSYNC_COLOR_* */
-    int32_t fill[4];            /* 0 .. 255 per channel: Y, U, V / R, G, B, A / gray */
+    int32_t format;             /* RSSYNC_COLOR_* or RSSYNC_COLOR16_* */
+    int32_t fill[4];            /* per channel: Y, U, V / R, G, B, A / gray; 0 .. 255, 16-bit formats: sample values, 0 .. 1023
+                                   (P010, I010) or 0 .. 65535 (GRAY16, P016), and luma.fill is not read */
 } rship_color_cfg;
 
 /* Stabilise n_frames colour frames: rship_stabilize_frames' memory rules and chunking, every plane of `in` of one kind

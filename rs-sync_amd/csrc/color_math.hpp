@@ -8,6 +8,7 @@
 //   lens    fx * 0.5, fy * 0.5, (cx - ox) * 0.5, (cy - oy) * 0.5; ro, k1 .. k4 unchanged        fp64 (color_chroma_camera)
 //   time    T_c = T + ro * (oy / height)                                                       fp64 (color_chroma_time)
 //   sample  rect_sample's taps and weights (color_taps) and its blend of four values (color_blend): bit for bit
+//   16 bit  the same blend on uint16 sample values (color_blend16), and P010's container: value = word >> 6, word = value << 6
 #pragma once
 
 #include <math.h>
@@ -58,6 +59,19 @@ RS_LHD uint8_t color_blend(float p00, float p01, float p10, float p11, float fx,
     const float val = top + fy * (bot - top);
     return (uint8_t)rintf(val);
 }
+
+// the blend on the sample values of a 16-bit container (include/rssync_color16.h): color_blend's three operations in its
+// order.  Every operation is monotone in its rounding, so the result lies within the four taps' range: no clamp.
+RS_LHD uint16_t color_blend16(float p00, float p01, float p10, float p11, float fx, float fy) {
+    const float top = p00 + fx * (p01 - p00);
+    const float bot = p10 + fx * (p11 - p10);
+    const float val = top + fy * (bot - top);
+    return (uint16_t)rintf(val);
+}
+
+// P010: ten bits in the high end of the word; the low six are ignored on input and zero on output
+RS_LHD uint32_t color_p010_unpack(uint32_t word) { return word >> 6; }
+RS_LHD uint32_t color_p010_pack(uint32_t value) { return value << 6; }
 
 } // namespace rs
 

@@ -28,6 +28,7 @@
 //                      the row table against a target, the warp, the border coverage sweep (kernels/stabilize.hpp).
 //   color_*_kernel     NV12, I420 and RGBA32 frames stabilised with all planes of a frame in one launch: both row tables,
 //                      the 4:2:0 warp per chroma sample with its 2 x 2 luma pixels, the RGBA warp (kernels/color.hpp).
+//   color16_*_kernel   the same for 16-bit containers: GRAY16, P010, P016 and I010 (kernels/color16.hpp).
 // Data layout and the roofline that bounds each kernel: DESIGN.md.
 // The kernels live in kernels/*.hpp (one header each, included below); this file holds the
 // device context and the launchers.
@@ -85,6 +86,7 @@ using rs::f4;
 #include "kernels/rectify.hpp"
 #include "kernels/stabilize.hpp"
 #include "kernels/color.hpp"
+#include "kernels/color16.hpp"
 
 // ===========================================================================
 // host side of the C-ABI
@@ -4204,23 +4206,33 @@ struct ColorPlane {
     uint32_t rows;
 };
 
-// the planes of a width x height frame -> their number
+// the 16-bit formats (include/rssync_color16.h): GRAY16 16, P010 17, P016 18, I010 19
+bool color_is_16(int format) { return format >= 16 && format <= 19; }
+
+// the 8-bit format whose planes and geometry a format has: GRAY16 -> GRAY8, P010 and P016 -> NV12, I010 -> I420
+int color_sibling(int format) { return format == 16 ? 0 : (format == 17 || format == 18) ? 1 : format == 19 ? 2 : format; }
+
+// the planes of a width x height frame -> their number; a 16-bit format's rows are twice its sibling's bytes
 int color_planes(int format, uint32_t w, uint32_t h, ColorPlane* pl) {
-    switch (format) {
-    case 0: pl[0] = {w, h}; return 1;
-    case 1: pl[0] = {w, h}; pl[1] = {w, h / 2}; return 2;
-    case 2: pl[0] = {w, h}; pl[1] = pl[2] = {w / 2, h / 2}; return 3;
+    const size_t b = color_is_16(format) ? 2 : 1;
+    switch (color_sibling(format)) {
+    case 0: pl[0] = {b * w, h}; return 1;
+    case 1: pl[0] = {b * w, h}; pl[1] = {b * w, h / 2}; return 2;
+    case 2: pl[0] = {b * w, h}; pl[1] = pl[2] = {b * (w / 2), h / 2}; return 3;
     case 3: pl[0] = {(size_t)w * 4, h}; return 1;
     }
     return 0;
 }
 
-bool color_is_yuv(int format) { return format == 1 || format == 2; }
+bool color_is_yuv(int format) { return color_sibling(format) == 1 || color_sibling(format) == 2; }
+
+// the largest sample value of a format: 8 bits, P010's and I010's ten, GRAY16's and P016's sixteen
+int32_t color_max(int format) { return !color_is_16(format) ? 255 : (format == 17 || format == 19) ? 1023 : 65535; }
 
 int color_check(rship_ctx* c, const rship_color_cfg* g) {
-    if (!g || g->format < 0 || g->format > 3) return set_err(c, "color: bad configuration");
+    if (!g || !((g->format >= 0 && g->format <= 3) || color_is_16(g->format))) return set_err(c, "color: bad configuration");
     for (int k = 0; k < 4; ++k)
-        if (g->fill[k] < 0 || g->fill[k] > 255) return set_err(c, "color: bad configuration");
+        if (g->fill[k] < 0 || g->fill[k] > color_max(g->format)) return set_err(c, "color: bad configuration");
     if (stab_check(c, &g->luma)) return 1;
     if (color_is_yuv(g->format)) {
         const rship_stabilize_cfg &l = g->luma, &k = g->chroma;
@@ -4264,7 +4276,8 @@ int rship_color_frames(rship_ctx* c, const rship_color_image* in, uint32_t n_fra
     if (!in || !out || !frame_times) return set_err(c, "color: null pointer");
     if (!n_frames) return 0;
     rship_stabilize_cfg L = cfg->luma;
-    L.fill = cfg->fill[0];
+    const bool wide = color_is_16(cfg->format);
+    if (!wide) L.fill = cfg->fill[0]; // (the 16-bit kernels take their fills as arguments of their own)
     const bool yuv = color_is_yuv(cfg->format);
     const uint32_t h = L.height, ow = L.out_width, oh = L.out_height, hc = yuv ? h / 2 : 0;
     ColorPlane pi[3] = {}, po[3] = {};
@@ -4273,6 +4286,9 @@ int rship_color_frames(rship_ctx* c, const rship_color_image* in, uint32_t n_fra
     size_t in_bytes = 0, out_bytes = 0;
     for (int k = 0; k < np; ++k) {
         if (!in->plane[k] || !out->plane[k]) return set_err(c, "color: null pointer");
+        if (wide && (((uintptr_t)in->plane[k] | (uintptr_t)out->plane[k] | in->pitch[k] | out->pitch[k]) & 1u ||
+                     (n_frames > 1 && ((in->stride[k] | out->stride[k]) & 1u))))
+            return set_err(c, "color: alignment: planes, pitches and strides of 16-bit samples must be multiples of 2");
         if (in->pitch[k] < pi[k].row_bytes || out->pitch[k] < po[k].row_bytes ||
             (n_frames > 1 && (in->stride[k] < in->pitch[k] * pi[k].rows || out->stride[k] < out->pitch[k] * po[k].rows)))
             return set_err(c, "color: pitch or frame stride too small");
@@ -4323,6 +4339,10 @@ int rship_color_frames(rship_ctx* c, const rship_color_image* in, uint32_t n_fra
     A.out_height = oh;
     A.iterations = L.iterations;
     A.fill = (uint32_t)cfg->fill[0] | (uint32_t)cfg->fill[1] << 8 | (uint32_t)cfg->fill[2] << 16 | (uint32_t)cfg->fill[3] << 24;
+    // the 16-bit kernels' fills as stored words: P010's values sit in the ten high bits
+    const uint32_t sh16 = cfg->format == 17 ? 6 : 0;
+    const uint32_t fill16_y = (uint32_t)cfg->fill[0] << sh16, fill16_uv = (uint32_t)cfg->fill[1] << sh16 | (uint32_t)cfg->fill[2] << (16 + sh16);
+    if (wide) A.fill = 0;
     // the chunk pipeline of rship_rectify_frames: chunk j in slot j & 1, uploads and downloads on the copy stream
     auto upload = [&](int slot, bool reused, uint32_t f0, uint32_t cnt) -> int {
         if (reused) RS_HIP(hipStreamWaitEvent(c->copy_stream, c->trk_k[slot], 0));
@@ -4377,9 +4397,26 @@ int rship_color_frames(rship_ctx* c, const rship_color_image* in, uint32_t n_fra
             if (lens_cam) hipLaunchKernelGGL((color_yuv_kernel<0, false>), grid_c, dim3(256), 0, c->stream, A);
             else hipLaunchKernelGGL((color_yuv_kernel<1, false>), grid_c, dim3(256), 0, c->stream, A);
             break;
-        default:
+        case 3:
             if (lens_cam) hipLaunchKernelGGL((color_rgba_kernel<0>), grid, dim3(256), 0, c->stream, A);
             else hipLaunchKernelGGL((color_rgba_kernel<1>), grid, dim3(256), 0, c->stream, A);
+            break;
+        case 16:
+            if (lens_cam) hipLaunchKernelGGL((color16_gray_kernel<0>), grid, dim3(256), 0, c->stream, A, fill16_y);
+            else hipLaunchKernelGGL((color16_gray_kernel<1>), grid, dim3(256), 0, c->stream, A, fill16_y);
+            break;
+        case 17:
+            if (lens_cam) hipLaunchKernelGGL((color16_yuv_kernel<0, true, 6>), grid_c, dim3(256), 0, c->stream, A, fill16_y, fill16_uv);
+            else hipLaunchKernelGGL((color16_yuv_kernel<1, true, 6>), grid_c, dim3(256), 0, c->stream, A, fill16_y, fill16_uv);
+            break;
+        case 18:
+            if (lens_cam) hipLaunchKernelGGL((color16_yuv_kernel<0, true, 0>), grid_c, dim3(256), 0, c->stream, A, fill16_y, fill16_uv);
+            else hipLaunchKernelGGL((color16_yuv_kernel<1, true, 0>), grid_c, dim3(256), 0, c->stream, A, fill16_y, fill16_uv);
+            break;
+        case 19:
+            if (lens_cam) hipLaunchKernelGGL((color16_yuv_kernel<0, false, 0>), grid_c, dim3(256), 0, c->stream, A, fill16_y, fill16_uv);
+            else hipLaunchKernelGGL((color16_yuv_kernel<1, false, 0>), grid_c, dim3(256), 0, c->stream, A, fill16_y, fill16_uv);
+            break;
         }
         RS_HIP(hipGetLastError());
         RS_HIP(hipEventRecord(c->trk_k[slot], c->stream));

@@ -715,8 +715,9 @@ class SyncProblem:
         return stabilize.stabilize_zoom(self, width, height, lens, frame_times, delay, zooms, **params)
 
     def stabilize_color(self, fmt, frames, frame_times, lens, delay, **params):
-        """Colour frames (rssync_amd.color: GRAY8, NV12, I420, RGBA32) rendered at the smoothed path's orientations, or at
-        `targets`, all planes of a frame in one pass (include/rssync_color.h) -> (frames in the layout of `frames`,
+        """Colour frames (rssync_amd.color: GRAY8, NV12, I420, RGBA32, and with uint16 samples GRAY16, P010, P016, I010)
+        rendered at the smoothed path's orientations, or at `targets`, all planes of a frame in one pass
+        (include/rssync_color.h, include/rssync_color16.h) -> (frames in the layout of `frames`,
         n_outside (n, 2)).  params: targets, out_size, out, chroma_site, fills, sigma, zoom, camera, out_camera,
         iterations, fill."""
         from . import color
