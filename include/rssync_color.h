@@ -6,7 +6,10 @@
  * the same size (rssync_stabilize.h's anchor).
  *
  * Plane 0 (Y, gray, RGBA) is rssync_stabilize_frames of that plane: same map, same bytes; RGBA has one position per
- * pixel and the sampler's arithmetic applies per channel.
+ * pixel and the sampler's arithmetic applies per channel.  params->stab.filter chooses the sampler of every plane and
+ * channel (rssync_stabilize.h, "Sampling"): with RSSYNC_FILTER_BICUBIC the eight weights of a position are computed once
+ * and shared by U and V and by R, G, B and A; every statement here that names rssync_stabilize_frames holds with that
+ * filter in both calls.  rssync_color_map checks the field and does not depend on it.
  *
  * A 4:2:0 chroma plane is the image of a camera of its own.  Chroma sample (cu, cv) sits at luma position
  * (2 cu + ox, 2 cv + oy): RSSYNC_CHROMA_CENTER (ox, oy) = (0.5, 0.5), RSSYNC_CHROMA_LEFT (0, 0.5).  All of this in fp64:

@@ -14,12 +14,18 @@
  *   P016     NV12's                         the word                         value          0 .. 65535
  *   I010     I420's (yuv420p10le)           the word as written              value          0 .. 1023
  * Row widths in bytes are twice the 8-bit sibling's: GRAY16 2 W; P010 and P016 2 W (Y) and 2 W (UV, H / 2 rows); I010 2 W, W, W.
- * I010's words are taken as written: a word above 1023 is not masked, and the result lies within the range of its taps.
+ * I010's words are taken as written: a word above 1023 is not masked, and the result lies within the range of its taps
+ * (with the bilinear sampler only: see below).
  *
  * The map of a plane is the sibling format's rssync_color_map, bit for bit (ask it with RSSYNC_COLOR_GRAY8, _NV12 or _I420).
  * The inside test, the taps and the weights are the 8-bit sampler's; the blend is its three fp32 operations in its order on
  * the sample values, rounded to nearest even into uint16.  By monotone rounding the result never leaves the range of the
  * four taps.  U and V are sampled at the one position.  P010's output words have their low six bits zero.
+ *
+ * With params->stab.filter == RSSYNC_FILTER_BICUBIC (rssync_stabilize.h, "Sampling") the sixteen taps are blended on the
+ * sample values -- P010's unpacked with >> 6 before and packed with << 6 after, as above -- and the kernel overshoots, so
+ * the value is clamped to the format's range before it is rounded: 0 .. 65535 for GRAY16 and P016, 0 .. 1023 for P010 and
+ * for I010.  I010's taps are still taken as written, but its result is then clamped to 1023 whatever they hold.
  *
  * Fill.  fill_set == 0: Y and gray get stab.fill << (depth - 8) (stab.fill still 0 .. 255), U and V 1 << (depth - 1), depth
  * 10 for P010 and I010 and 16 for GRAY16 and P016.  fill_set != 0: fill[] is used in the format's order (Y, U, V / gray) in

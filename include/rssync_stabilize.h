@@ -24,8 +24,21 @@
  * formed in fp32: exactly 1 when the sizes agree), the rectifier's iteration, `iterations` times:
  * M = M_i + (y' - i)(M_(i+1) - M_i) with y' = y clamped to [0, height - 1] and i = floor(y'), (x, y) = project(M r) with
  * the input lens.  The last (x, y) is the source position in the input frame: inside when 0 <= x <= width - 1 and
- * 0 <= y <= height - 1.  Sampling is the rectifier's bilinear sampler, bit for bit; pixels whose source is outside get
- * `fill`.
+ * 0 <= y <= height - 1.  Sampling is the rectifier's bilinear sampler, bit for bit (params->filter ==
+ * RSSYNC_FILTER_BILINEAR, the default), or the bicubic one below; pixels whose source is outside get `fill`.
+ *
+ * Sampling, RSSYNC_FILTER_BICUBIC: Keys' cubic convolution with a = -0.5 (Catmull-Rom) over 4 x 4 taps.  For an inside
+ * position (x, y): ix = min(floor(x), width - 2), tx = x - ix (in [0, 1], 1 on the last column only), iy and ty
+ * likewise; the tap columns are clamp(ix + d, 0, width - 1) for d = -1, 0, 1, 2 and the rows likewise -- the edge is
+ * replicated, so the inside rule, the map and n_outside are those of the bilinear sampler.  The weights of t are
+ *     w0 = ((1 - 0.5 t) t - 0.5) t     w1 = ((1.5 t - 2.5) t) t + 1
+ *     w2 = ((2 - 1.5 t) t + 0.5) t     w3 = ((0.5 t - 0.5) t) t,
+ * exactly (-0, 1, 0, 0) at t = 0 and (0, 0, 1, 0) at t = 1: an integer position returns its sample, and a camera at rest
+ * is still the identity.  Per tap row j, r_j = (wx0 p_j0 + wx1 p_j1) + (wx2 p_j2 + wx3 p_j3); then
+ * val = (wy0 r_0 + wy1 r_1) + (wy2 r_2 + wy3 r_3), clamped to 0 .. 255 (the kernel overshoots at edges in the picture)
+ * and rounded to the nearest integer, ties to even.  Every operation is one fp32 operation rounded on its own, in this
+ * order.  The kernel keeps more detail than the bilinear one (noise resampled at a fractional position keeps a standard
+ * deviation of 60.9 of 73.9 grey levels instead of 50.2); it costs sixteen taps a pixel instead of four.
  *
  * The anchor: with targets == NULL, sigma = 0, all-default parameters and out_width x out_height == width x height the
  * map equals rssync_rectify_map at its default ref_row bit for bit and the frames equal rssync_rectify_frames byte for
@@ -41,7 +54,7 @@
  * Errors follow rssync_set_panic_mode; each returns non-zero and leaves the problem usable: no gyro data installed; NULL
  * pointers; a frame whose row times plus delay leave the gyro's knots (only the path's taps are clamped); sigma negative
  * or non-finite; a zoom or a zooms[] entry <= 0 or non-finite; a non-finite or zero target; only some of fx, fy, cx, cy
- * given; camera outside the enum; sizes below 2; pitches below widths; iterations or fill out of range; out overlapping
+ * given; camera or filter outside its enum; sizes below 2; pitches below widths; iterations or fill out of range; out overlapping
  * the frames; a pointer into another device's memory.
  */
 #ifndef RSSYNC_STABILIZE_H
@@ -57,6 +70,7 @@ extern "C" {
 #endif
 
 enum { RSSYNC_CAMERA_LENS = 0, RSSYNC_CAMERA_PINHOLE = 1 };
+enum { RSSYNC_FILTER_BILINEAR = 0, RSSYNC_FILTER_BICUBIC = 1 };
 
 /* NULL or all zeros = all defaults */
 typedef struct rssync_stabilize_params {
@@ -67,6 +81,9 @@ typedef struct rssync_stabilize_params {
     int32_t camera;        /* RSSYNC_CAMERA_LENS: the input lens's k1 .. k4 on the output camera; RSSYNC_CAMERA_PINHOLE: none */
     int32_t iterations;    /* 1 .. 8; 0 = default: 3 */
     int32_t fill;          /* 0 .. 255: value of pixels whose source is outside the frame */
+    int32_t filter;        /* RSSYNC_FILTER_BILINEAR (0, the default) or RSSYNC_FILTER_BICUBIC: "Sampling" above.  Read by
+                              rssync_stabilize_frames; the map and the coverage check it and do not depend on it.  It lies in
+                              what was the struct's tail padding: the size stays 64 bytes, the offset is 60 */
 } rssync_stabilize_params;
 
 /* The smoothed path at n frame times (host): quats is n x {w, x, y, z}, host or device memory. */

@@ -28,6 +28,7 @@ import numpy as np
 from .problem import RsSyncError, load_library
 from .rectify import _check, _is_torch, _lens
 from .stabilize import StabilizeParams, _Cfg as _StabCfg, _targets, _times, params as _stab_params, CAMERA_LENS, DEFAULT_ITERATIONS
+from .stabilize import FILTER_BILINEAR, FILTER_BICUBIC  # noqa: F401  (re-exported: stabilize_color(..., filter=FILTER_BICUBIC))
 
 _PD = C.POINTER(C.c_double)
 _SZ = C.c_size_t
@@ -99,7 +100,8 @@ def _lib_of(problem):
 def params(chroma_site=CHROMA_CENTER, fills=None, **kw):
     """fills: None = the defaults from `fill` (U, V = 128, A = 255; 16-bit formats: `fill` << (depth - 8) and
     1 << (depth - 1)), else the values in the format's order, 16-bit formats: in sample values; kw: the
-    stabiliser's sigma, zoom, camera, out_camera, iterations, fill.  Everything is handed on as written."""
+    stabiliser's sigma, zoom, camera, out_camera, iterations, fill, filter (FILTER_BICUBIC: every plane and channel through
+    the Catmull-Rom sampler, clamped to the format's range).  Everything is handed on as written."""
     prm = ColorParams()
     prm.stab = _stab_params(**kw)
     prm.chroma_site = int(chroma_site)
@@ -188,7 +190,7 @@ def stabilize_color(problem, fmt, frames, frame_times, lens, delay, targets=None
                     fills=None, **kw):
     """-> (stabilised frames in the layout of `frames` -- `out` if given --, n_outside (n, 2) uint64: filled pixels of plane
     0, filled chroma samples).  out_size: (out_width, out_height), None = the input's.  kw: sigma, zoom, camera,
-    out_camera, iterations, fill."""
+    out_camera, iterations, fill, filter."""
     lib = _lib_of(problem)
     planes = _as_planes(fmt, frames)
     n, h, w = _size(fmt, planes)
@@ -246,7 +248,7 @@ def chroma_config(lens, width, height, out_width, out_height, chroma_site=CHROMA
 
 
 def stabilize_color_budget(problem, fmt, frames, frame_times, lens, delay, budget_bytes, out_size=None, sigma=0.0,
-                           chroma_site=CHROMA_CENTER, iterations=DEFAULT_ITERATIONS, fills=None):
+                           chroma_site=CHROMA_CENTER, iterations=DEFAULT_ITERATIONS, fills=None, filter=FILTER_BILINEAR):
     """stabilize_color along the path through the internal launcher with its device budget for the chunk slots given
     (tests: small frames that span several chunks).  LENS camera, zoom 1; fills: None = the header's defaults for fill 0.
     numpy frames -> (planes, n_outside (n, 2))"""
@@ -265,7 +267,8 @@ def stabilize_color_budget(problem, fmt, frames, frame_times, lens, delay, budge
 
     def stab_cfg(w_, h_, ow_, oh_, lens_, cam_):
         return _StabCfg(w_, h_, ow_, oh_, (C.c_double * 9)(*lens_), (C.c_double * 4)(*cam_), start, fs, n_knots, float(delay), float(sigma),
-                        CAMERA_LENS, int(iterations), 0 if fmt in SIBLING else int(fills[0]))   # (16-bit: cfg.fill alone is read)
+                        CAMERA_LENS, int(iterations), 0 if fmt in SIBLING else int(fills[0]),    # (16-bit: cfg.fill alone is read)
+                        int(filter))
 
     cfg = _Cfg()
     cfg.luma = stab_cfg(w, h, ow, oh, L, cam)

@@ -11,8 +11,12 @@
 #include "stabilize_host.hpp"
 
 #include <cmath>
+#include <cstddef>
 #include <string>
 #include <vector>
+
+// the stabiliser's struct leads the colour parameters: its new last field must not have moved what follows
+static_assert(offsetof(rssync_color_params, chroma_site) == 64 && sizeof(rssync_color_params) == 88, "rssync_color_params moved");
 
 using rssync_host::guarded;
 using rssync_host::panic;

@@ -29,6 +29,7 @@
 //   color_*_kernel     NV12, I420 and RGBA32 frames stabilised with all planes of a frame in one launch: both row tables,
 //                      the 4:2:0 warp per chroma sample with its 2 x 2 luma pixels, the RGBA warp (kernels/color.hpp).
 //   color16_*_kernel   the same for 16-bit containers: GRAY16, P010, P016 and I010 (kernels/color16.hpp).
+//   *bicubic*_kernel   the siblings of the kernels that write pixels with the 4 x 4 Catmull-Rom sampler (kernels/resample.hpp).
 // Data layout and the roofline that bounds each kernel: DESIGN.md.
 // The kernels live in kernels/*.hpp (one header each, included below); this file holds the
 // device context and the launchers.
@@ -61,6 +62,7 @@
 #include "rectify_math.hpp"
 #include "stabilize_math.hpp"
 #include "color_math.hpp"
+#include "resample_math.hpp"
 #include "gyro_math.hpp"
 #include "gyro_signal_math.hpp"
 #include "window_plan.hpp"
@@ -87,6 +89,7 @@ using rs::f4;
 #include "kernels/stabilize.hpp"
 #include "kernels/color.hpp"
 #include "kernels/color16.hpp"
+#include "kernels/resample.hpp"
 
 // ===========================================================================
 // host side of the C-ABI
@@ -3922,7 +3925,7 @@ constexpr size_t kStabCoverTables = 64ull << 20; // device bytes of row tables a
 int stab_check(rship_ctx* c, const rship_stabilize_cfg* g) {
     if (!g || g->width < 2 || g->height < 2 || g->width > 65536 || g->height > 65536 || g->out_width < 2 || g->out_height < 2 ||
         g->out_width > 65536 || g->out_height > 65536 || g->iterations < 1 || g->iterations > 8 || g->fill < 0 || g->fill > 255 ||
-        (g->camera != 0 && g->camera != 1) || !(g->sigma >= 0.0) || !std::isfinite(g->sigma))
+        (g->camera != 0 && g->camera != 1) || (g->filter != 0 && g->filter != 1) || !(g->sigma >= 0.0) || !std::isfinite(g->sigma))
         return set_err(c, "stabilize: bad configuration");
     if (c->n_knots < 2 || !c->coef64.p || g->n_knots != c->n_knots) return set_err(c, "stabilize: the device holds no spline table of the gyro data");
     return 0;
@@ -4016,6 +4019,13 @@ StabArgs stab_args(rship_ctx* c, const rship_stabilize_cfg* g) {
 template <bool MAP>
 void stab_launch(rship_ctx* c, const rship_stabilize_cfg* g, const StabArgs& A, uint32_t cnt) {
     const dim3 grid((g->out_width + kRectTW - 1) / kRectTW, (g->out_height + kRectTH - 1) / kRectTH, cnt);
+    if (!MAP && g->filter == 1) { // RSSYNC_FILTER_BICUBIC (kernels/resample.hpp); the map does not depend on the filter
+        if (g->camera == 0)
+            hipLaunchKernelGGL((stabilize_bicubic_kernel<0>), grid, dim3(256), 0, c->stream, A);
+        else
+            hipLaunchKernelGGL((stabilize_bicubic_kernel<1>), grid, dim3(256), 0, c->stream, A);
+        return;
+    }
     if (g->camera == 0)
         hipLaunchKernelGGL((stabilize_kernel<0, MAP>), grid, dim3(256), 0, c->stream, A);
     else
@@ -4239,7 +4249,7 @@ int color_check(rship_ctx* c, const rship_color_cfg* g) {
         if (stab_check(c, &k)) return 1;
         if ((l.width | l.height | l.out_width | l.out_height) & 1u || k.width != l.width / 2 || k.height != l.height / 2 ||
             k.out_width != l.out_width / 2 || k.out_height != l.out_height / 2 || k.camera != l.camera || k.iterations != l.iterations ||
-            !std::isfinite(g->chroma_time))
+            k.filter != l.filter || !std::isfinite(g->chroma_time))
             return set_err(c, "color: bad configuration");
     }
     return 0;
@@ -4380,7 +4390,7 @@ int rship_color_frames(rship_ctx* c, const rship_color_image* in, uint32_t n_fra
         }
         const dim3 grid((ow + kRectTW - 1) / kRectTW, (oh + kRectTH - 1) / kRectTH, cnt);
         const dim3 grid_c((ow / 2 + kRectTW - 1) / kRectTW, (oh / 2 + kRectTH - 1) / kRectTH, cnt);
-        const bool lens_cam = L.camera == 0;
+        const bool lens_cam = L.camera == 0, cubic = L.filter == 1; // cubic: the siblings of kernels/resample.hpp
         switch (cfg->format) {
         case 0:
             G.rows_tab = A.luma.rows_tab;
@@ -4390,31 +4400,45 @@ int rship_color_frames(rship_ctx* c, const rship_color_image* in, uint32_t n_fra
             stab_launch<false>(c, &L, G, cnt);
             break;
         case 1:
-            if (lens_cam) hipLaunchKernelGGL((color_yuv_kernel<0, true>), grid_c, dim3(256), 0, c->stream, A);
+            if (cubic && lens_cam) hipLaunchKernelGGL((bicubic_yuv_kernel<0, true>), grid_c, dim3(256), 0, c->stream, A);
+            else if (cubic) hipLaunchKernelGGL((bicubic_yuv_kernel<1, true>), grid_c, dim3(256), 0, c->stream, A);
+            else if (lens_cam) hipLaunchKernelGGL((color_yuv_kernel<0, true>), grid_c, dim3(256), 0, c->stream, A);
             else hipLaunchKernelGGL((color_yuv_kernel<1, true>), grid_c, dim3(256), 0, c->stream, A);
             break;
         case 2:
-            if (lens_cam) hipLaunchKernelGGL((color_yuv_kernel<0, false>), grid_c, dim3(256), 0, c->stream, A);
+            if (cubic && lens_cam) hipLaunchKernelGGL((bicubic_yuv_kernel<0, false>), grid_c, dim3(256), 0, c->stream, A);
+            else if (cubic) hipLaunchKernelGGL((bicubic_yuv_kernel<1, false>), grid_c, dim3(256), 0, c->stream, A);
+            else if (lens_cam) hipLaunchKernelGGL((color_yuv_kernel<0, false>), grid_c, dim3(256), 0, c->stream, A);
             else hipLaunchKernelGGL((color_yuv_kernel<1, false>), grid_c, dim3(256), 0, c->stream, A);
             break;
         case 3:
-            if (lens_cam) hipLaunchKernelGGL((color_rgba_kernel<0>), grid, dim3(256), 0, c->stream, A);
+            if (cubic && lens_cam) hipLaunchKernelGGL((bicubic_rgba_kernel<0>), grid, dim3(256), 0, c->stream, A);
+            else if (cubic) hipLaunchKernelGGL((bicubic_rgba_kernel<1>), grid, dim3(256), 0, c->stream, A);
+            else if (lens_cam) hipLaunchKernelGGL((color_rgba_kernel<0>), grid, dim3(256), 0, c->stream, A);
             else hipLaunchKernelGGL((color_rgba_kernel<1>), grid, dim3(256), 0, c->stream, A);
             break;
         case 16:
-            if (lens_cam) hipLaunchKernelGGL((color16_gray_kernel<0>), grid, dim3(256), 0, c->stream, A, fill16_y);
+            if (cubic && lens_cam) hipLaunchKernelGGL((bicubic16_gray_kernel<0>), grid, dim3(256), 0, c->stream, A, fill16_y);
+            else if (cubic) hipLaunchKernelGGL((bicubic16_gray_kernel<1>), grid, dim3(256), 0, c->stream, A, fill16_y);
+            else if (lens_cam) hipLaunchKernelGGL((color16_gray_kernel<0>), grid, dim3(256), 0, c->stream, A, fill16_y);
             else hipLaunchKernelGGL((color16_gray_kernel<1>), grid, dim3(256), 0, c->stream, A, fill16_y);
             break;
         case 17:
-            if (lens_cam) hipLaunchKernelGGL((color16_yuv_kernel<0, true, 6>), grid_c, dim3(256), 0, c->stream, A, fill16_y, fill16_uv);
+            if (cubic && lens_cam) hipLaunchKernelGGL((bicubic16_yuv_kernel<0, true, 6>), grid_c, dim3(256), 0, c->stream, A, fill16_y, fill16_uv);
+            else if (cubic) hipLaunchKernelGGL((bicubic16_yuv_kernel<1, true, 6>), grid_c, dim3(256), 0, c->stream, A, fill16_y, fill16_uv);
+            else if (lens_cam) hipLaunchKernelGGL((color16_yuv_kernel<0, true, 6>), grid_c, dim3(256), 0, c->stream, A, fill16_y, fill16_uv);
             else hipLaunchKernelGGL((color16_yuv_kernel<1, true, 6>), grid_c, dim3(256), 0, c->stream, A, fill16_y, fill16_uv);
             break;
         case 18:
-            if (lens_cam) hipLaunchKernelGGL((color16_yuv_kernel<0, true, 0>), grid_c, dim3(256), 0, c->stream, A, fill16_y, fill16_uv);
+            if (cubic && lens_cam) hipLaunchKernelGGL((bicubic16_yuv_kernel<0, true, 0>), grid_c, dim3(256), 0, c->stream, A, fill16_y, fill16_uv);
+            else if (cubic) hipLaunchKernelGGL((bicubic16_yuv_kernel<1, true, 0>), grid_c, dim3(256), 0, c->stream, A, fill16_y, fill16_uv);
+            else if (lens_cam) hipLaunchKernelGGL((color16_yuv_kernel<0, true, 0>), grid_c, dim3(256), 0, c->stream, A, fill16_y, fill16_uv);
             else hipLaunchKernelGGL((color16_yuv_kernel<1, true, 0>), grid_c, dim3(256), 0, c->stream, A, fill16_y, fill16_uv);
             break;
         case 19:
-            if (lens_cam) hipLaunchKernelGGL((color16_yuv_kernel<0, false, 0>), grid_c, dim3(256), 0, c->stream, A, fill16_y, fill16_uv);
+            if (cubic && lens_cam) hipLaunchKernelGGL((bicubic16_yuv_kernel<0, false, 0>), grid_c, dim3(256), 0, c->stream, A, fill16_y, fill16_uv);
+            else if (cubic) hipLaunchKernelGGL((bicubic16_yuv_kernel<1, false, 0>), grid_c, dim3(256), 0, c->stream, A, fill16_y, fill16_uv);
+            else if (lens_cam) hipLaunchKernelGGL((color16_yuv_kernel<0, false, 0>), grid_c, dim3(256), 0, c->stream, A, fill16_y, fill16_uv);
             else hipLaunchKernelGGL((color16_yuv_kernel<1, false, 0>), grid_c, dim3(256), 0, c->stream, A, fill16_y, fill16_uv);
             break;
         }

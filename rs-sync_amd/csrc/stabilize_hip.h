@@ -28,6 +28,8 @@ typedef struct rship_stabilize_cfg {
     int32_t camera;                 /* RSSYNC_CAMERA_LENS / RSSYNC_CAMERA_PINHOLE */
     int32_t iterations;             /* 1 .. 8 */
     int32_t fill;                   /* 0 .. 255 */
+    int32_t filter;                 /* RSSYNC_FILTER_BILINEAR / RSSYNC_FILTER_BICUBIC; in the struct's former tail padding
+                                       (offset 172 of 176), so a zero-filled configuration of old is bilinear */
 } rship_stabilize_cfg;
 
 /* The smoothed path at n frame times (host): quats [n][4] {w, x, y, z}, host or device.  cfg: lens[0] (ro), start, fs,

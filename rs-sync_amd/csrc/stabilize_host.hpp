@@ -9,8 +9,14 @@
 #include "stabilize_hip.h"
 
 #include <cmath>
+#include <cstddef>
 #include <string>
 #include <vector>
+
+// `filter` took the place of tail padding: callers built against the nine-field struct keep working and pass 0 there
+// only if they zero-filled it, as the header's "all zeros = all defaults" demands
+static_assert(sizeof(rssync_stabilize_params) == 64 && offsetof(rssync_stabilize_params, filter) == 60, "rssync_stabilize_params moved");
+static_assert(sizeof(rship_stabilize_cfg) == 176 && offsetof(rship_stabilize_cfg, filter) == 172, "rship_stabilize_cfg moved");
 
 namespace rssync_stab_host {
 
@@ -88,6 +94,9 @@ inline rship_stabilize_cfg resolve(rssync_problem* p, size_t width, size_t heigh
     c.cam[1] = c.cam[1] * zoom;
     if (q.camera != RSSYNC_CAMERA_LENS && q.camera != RSSYNC_CAMERA_PINHOLE) panic("stabilize: camera must be RSSYNC_CAMERA_LENS or RSSYNC_CAMERA_PINHOLE");
     c.camera = q.camera;
+    if (q.filter != RSSYNC_FILTER_BILINEAR && q.filter != RSSYNC_FILTER_BICUBIC)
+        panic("stabilize: filter must be RSSYNC_FILTER_BILINEAR or RSSYNC_FILTER_BICUBIC");
+    c.filter = q.filter;
     c.iterations = q.iterations ? q.iterations : 3;
     if (c.iterations < 1 || c.iterations > 8) panic("stabilize: iterations must be 1 .. 8");
     if (q.fill < 0 || q.fill > 255) panic("stabilize: fill must be 0 .. 255");

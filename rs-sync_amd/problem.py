@@ -700,7 +700,8 @@ class SyncProblem:
 
     def stabilize_frames(self, frames, frame_times, lens, delay, **params):
         """The frames rendered at the smoothed path's orientations, or at `targets` -> (frames of the same kind,
-        n_outside (n,)).  params: targets, out_size, out, sigma, zoom, camera, out_camera, iterations, fill."""
+        n_outside (n,)).  params: targets, out_size, out, sigma, zoom, camera, out_camera, iterations, fill, filter
+        (stabilize.FILTER_BILINEAR, the default, or FILTER_BICUBIC)."""
         from . import stabilize
         return stabilize.stabilize_frames(self, frames, frame_times, lens, delay, **params)
 
@@ -719,7 +720,7 @@ class SyncProblem:
         rendered at the smoothed path's orientations, or at `targets`, all planes of a frame in one pass
         (include/rssync_color.h, include/rssync_color16.h) -> (frames in the layout of `frames`,
         n_outside (n, 2)).  params: targets, out_size, out, chroma_site, fills, sigma, zoom, camera, out_camera,
-        iterations, fill."""
+        iterations, fill, filter."""
         from . import color
         return color.stabilize_color(self, fmt, frames, frame_times, lens, delay, **params)
 

@@ -25,20 +25,22 @@ _PD = C.POINTER(C.c_double)
 _SZ = C.c_size_t
 
 CAMERA_LENS, CAMERA_PINHOLE = 0, 1
+FILTER_BILINEAR, FILTER_BICUBIC = 0, 1
 DEFAULT_ITERATIONS = 3
 
 
 class StabilizeParams(C.Structure):
     """rssync_stabilize_params: zeros = the defaults"""
     _fields_ = [("sigma", C.c_double), ("zoom", C.c_double), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double),
-                ("cy", C.c_double), ("camera", C.c_int32), ("iterations", C.c_int32), ("fill", C.c_int32)]
+                ("cy", C.c_double), ("camera", C.c_int32), ("iterations", C.c_int32), ("fill", C.c_int32), ("filter", C.c_int32)]
 
 
 class _Cfg(C.Structure):
     """rship_stabilize_cfg (csrc/stabilize_hip.h), for the tests' call of the internal launcher with a chunk budget"""
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("out_width", C.c_uint32), ("out_height", C.c_uint32),
                 ("lens", C.c_double * 9), ("cam", C.c_double * 4), ("start", C.c_double), ("fs", C.c_double), ("n_knots", C.c_uint32),
-                ("delay", C.c_double), ("sigma", C.c_double), ("camera", C.c_int32), ("iterations", C.c_int32), ("fill", C.c_int32)]
+                ("delay", C.c_double), ("sigma", C.c_double), ("camera", C.c_int32), ("iterations", C.c_int32), ("fill", C.c_int32),
+                ("filter", C.c_int32)]
 
 
 _PP = C.POINTER(StabilizeParams)
@@ -80,10 +82,11 @@ def _lib_of(problem):
     return lib
 
 
-def params(sigma=0.0, zoom=1.0, camera=CAMERA_LENS, out_camera=None, iterations=DEFAULT_ITERATIONS, fill=0):
-    """out_camera: None = the lens's, scaled to the output; else (fx, fy, cx, cy).  Everything is handed on as written."""
+def params(sigma=0.0, zoom=1.0, camera=CAMERA_LENS, out_camera=None, iterations=DEFAULT_ITERATIONS, fill=0, filter=FILTER_BILINEAR):
+    """out_camera: None = the lens's, scaled to the output; else (fx, fy, cx, cy).  filter: FILTER_BILINEAR or
+    FILTER_BICUBIC (Catmull-Rom over 4 x 4 taps: sharper, sixteen taps a pixel).  Everything is handed on as written."""
     fx, fy, cx, cy = (0.0, 0.0, 0.0, 0.0) if out_camera is None else (float(v) for v in out_camera)
-    return StabilizeParams(float(sigma), float(zoom), fx, fy, cx, cy, int(camera), int(iterations), int(fill))
+    return StabilizeParams(float(sigma), float(zoom), fx, fy, cx, cy, int(camera), int(iterations), int(fill), int(filter))
 
 
 def _targets(targets, n):
@@ -127,7 +130,7 @@ def stabilize_path(problem, frame_times, ro, delay, sigma, out=None):
 def stabilize_map(problem, width, height, lens, frame_time, delay, target=None, out_size=None, **kw):
     """-> (out_height, out_width, 2) float32: the source position (x, y) in the input frame of every output pixel.
     target: (w, x, y, z), or None = the path at sigma.  out_size: (out_width, out_height), None = the input's.
-    kw: sigma, zoom, camera, out_camera, iterations."""
+    kw: sigma, zoom, camera, out_camera, iterations (and filter, which is checked and changes nothing)."""
     lib = _lib_of(problem)
     L = _lens(lens)
     ow, oh = (int(width), int(height)) if out_size is None else (int(out_size[0]), int(out_size[1]))
@@ -142,7 +145,7 @@ def stabilize_map(problem, width, height, lens, frame_time, delay, target=None, 
 
 def stabilize_frames(problem, frames, frame_times, lens, delay, targets=None, out_size=None, out=None, **kw):
     """-> (stabilised frames (n, out_height, out_width) uint8 -- `out` if given, else of the kind of `frames` --,
-    n_outside (n,) uint64).  kw: sigma, zoom, camera, out_camera, iterations, fill."""
+    n_outside (n,) uint64).  kw: sigma, zoom, camera, out_camera, iterations, fill, filter."""
     lib = _lib_of(problem)
     ptr, n, h, w, pitch, fstride, keep = _frames(frames)
     t = _times(frame_times, n)
@@ -189,7 +192,7 @@ def stabilize_zoom(problem, width, height, lens, frame_times, delay, zooms, **kw
 
 
 def stabilize_frames_budget(problem, frames, frame_times, lens, delay, budget_bytes, out_size=None, sigma=0.0,
-                            iterations=DEFAULT_ITERATIONS, fill=0):
+                            iterations=DEFAULT_ITERATIONS, fill=0, filter=FILTER_BILINEAR):
     """stabilize_frames along the path through the internal launcher with its device budget for the chunk slots given
     (tests: small frames that span several chunks).  LENS camera, zoom 1.  numpy frames -> (frames, n_outside)"""
     lib = _lib_of(problem)
@@ -201,7 +204,7 @@ def stabilize_frames_budget(problem, frames, frame_times, lens, delay, budget_by
     sx, sy = ow / w, oh / h
     cam = (C.c_double * 4)(L[1] * sx, L[2] * sy, L[3] * sx, L[4] * sy)
     cfg = _Cfg(w, h, ow, oh, (C.c_double * 9)(*L), cam, start, fs, n_knots, float(delay), float(sigma), CAMERA_LENS,
-               int(iterations), int(fill))
+               int(iterations), int(fill), int(filter))
     out = np.empty((n, oh, ow), np.uint8)
     outside = np.zeros(max(n, 1), np.uint64)
     ctx = C.c_void_p(problem.device_context())
