@@ -30,6 +30,8 @@
 //                      the 4:2:0 warp per chroma sample with its 2 x 2 luma pixels, the RGBA warp (kernels/color.hpp).
 //   color16_*_kernel   the same for 16-bit containers: GRAY16, P010, P016 and I010 (kernels/color16.hpp).
 //   *bicubic*_kernel   the siblings of the kernels that write pixels with the 4 x 4 Catmull-Rom sampler (kernels/resample.hpp).
+//   zoom_*_kernel      the dynamic zoom: every frame's smallest clear zoom by an in-kernel bisection, and the stabiliser's
+//                      warp with one output camera per frame (kernels/zoom.hpp).
 // Data layout and the roofline that bounds each kernel: DESIGN.md.
 // The kernels live in kernels/*.hpp (one header each, included below); this file holds the
 // device context and the launchers.
@@ -56,6 +58,7 @@
 #include "rectify_hip.h"
 #include "stabilize_hip.h"
 #include "color_hip.h"
+#include "zoom_hip.h"
 #include "device_math.hpp"
 #include "sync_math.hpp"
 #include "lens_math.hpp"
@@ -63,6 +66,7 @@
 #include "stabilize_math.hpp"
 #include "color_math.hpp"
 #include "resample_math.hpp"
+#include "zoom_math.hpp"
 #include "gyro_math.hpp"
 #include "gyro_signal_math.hpp"
 #include "window_plan.hpp"
@@ -90,6 +94,7 @@ using rs::f4;
 #include "kernels/color.hpp"
 #include "kernels/color16.hpp"
 #include "kernels/resample.hpp"
+#include "kernels/zoom.hpp"
 
 // ===========================================================================
 // host side of the C-ABI
@@ -4032,31 +4037,13 @@ void stab_launch(rship_ctx* c, const rship_stabilize_cfg* g, const StabArgs& A, 
         hipLaunchKernelGGL((stabilize_kernel<1, MAP>), grid, dim3(256), 0, c->stream, A);
 }
 
-} // namespace
-
-extern "C" {
-
-int rship_stabilize_path(rship_ctx* c, const double* frame_times, size_t n, const rship_stabilize_cfg* cfg, double* quats) {
-    DeviceGuard dev_guard(c);
-    if (!cfg || !(cfg->sigma >= 0.0) || !std::isfinite(cfg->sigma)) return set_err(c, "stabilize: bad configuration");
-    if (c->n_knots < 2 || !c->coef64.p || cfg->n_knots != c->n_knots) return set_err(c, "stabilize: the device holds no spline table of the gyro data");
-    if (!n) return 0;
-    if (!frame_times || !quats) return set_err(c, "stabilize: null pointer");
-    if (n > 0x7fffffffu) return set_err(c, "stabilize: too many frames");
-    bool on_dev = false;
-    if (rect_pointer(c, quats, "the path's orientations", &on_dev, "stabilize")) return 1;
-    if (ensure(c, c->rect_times, n * 8)) return 1;
-    RS_HIP(hipMemcpy(c->rect_times.p, frame_times, n * 8, hipMemcpyHostToDevice));
-    if (stab_fill_targets(c, cfg, nullptr, n)) return 1;
-    RS_HIP(hipMemcpyAsync(quats, c->stab_targets.p, n * 32, hipMemcpyDefault, c->stream));
-    return sync_stream(c);
-}
-
-int rship_stabilize_frames(rship_ctx* c, const uint8_t* frames, uint32_t n_frames, size_t pitch, size_t frame_stride,
-                           const double* frame_times, const double* targets, const rship_stabilize_cfg* cfg, uint8_t* out,
-                           size_t out_pitch, size_t out_stride, uint64_t* n_outside, size_t budget_bytes) {
-    DeviceGuard dev_guard(c);
-    if (stab_check(c, cfg)) return 1;
+// The chunk pipeline of the frames: rship_stabilize_frames' and rship_zoom_frames'.  launch(A, f0, cnt) enqueues the
+// kernel that renders the chunk's cnt frames, the first of which is frame f0 of the call; ray_map: the cached ray map of
+// cfg's output camera is needed.
+template <class Launch>
+int stab_frames_run(rship_ctx* c, const uint8_t* frames, uint32_t n_frames, size_t pitch, size_t frame_stride, const double* frame_times,
+                    const double* targets, const rship_stabilize_cfg* cfg, uint8_t* out, size_t out_pitch, size_t out_stride,
+                    uint64_t* n_outside, size_t budget_bytes, bool ray_map, Launch&& launch) {
     if (!frames || !out || !frame_times) return set_err(c, "stabilize: null pointer");
     if (!n_frames) return 0;
     const uint32_t w = cfg->width, h = cfg->height, ow = cfg->out_width, oh = cfg->out_height;
@@ -4075,7 +4062,7 @@ int rship_stabilize_frames(rship_ctx* c, const uint8_t* frames, uint32_t n_frame
     if (ensure(c, c->rect_times, (size_t)n_frames * 8) || ensure(c, c->rect_count, (size_t)n_frames * 8) || rect_events(c)) return 1;
     RS_HIP(hipMemcpy(c->rect_times.p, frame_times, (size_t)n_frames * 8, hipMemcpyHostToDevice));
     RS_HIP(hipMemsetAsync(c->rect_count.p, 0, (size_t)n_frames * 8, c->stream));
-    if (stab_fill_targets(c, cfg, targets, n_frames) || stab_rays(c, cfg)) return 1;
+    if (stab_fill_targets(c, cfg, targets, n_frames) || (ray_map && stab_rays(c, cfg))) return 1;
     StabRowsArgs R = stab_rows_args(c, cfg);
     StabArgs A = stab_args(c, cfg);
     // the chunk pipeline of rship_rectify_frames: chunk j in slot j & 1, uploads and downloads on the copy stream
@@ -4107,7 +4094,7 @@ int rship_stabilize_frames(rship_ctx* c, const uint8_t* frames, uint32_t n_frame
         else { A.src = s_in; A.src_pitch = w; A.src_stride = px_in; }
         if (dev_out) { A.dst = out + (size_t)f0 * out_stride; A.dst_pitch = out_pitch; A.dst_stride = out_stride; }
         else { A.dst = s_out; A.dst_pitch = ow; A.dst_stride = px_out; }
-        stab_launch<false>(c, cfg, A, cnt);
+        launch(A, f0, cnt);
         RS_HIP(hipGetLastError());
         RS_HIP(hipEventRecord(c->trk_k[slot], c->stream));
         used[slot] = true;
@@ -4123,6 +4110,35 @@ int rship_stabilize_frames(rship_ctx* c, const uint8_t* frames, uint32_t n_frame
     if (n_outside) RS_HIP(hipMemcpyAsync(n_outside, c->rect_count.p, (size_t)n_frames * 8, hipMemcpyDeviceToHost, c->stream));
     RS_HIP(hipStreamSynchronize(c->copy_stream));
     return sync_stream(c);
+}
+
+} // namespace
+
+extern "C" {
+
+int rship_stabilize_path(rship_ctx* c, const double* frame_times, size_t n, const rship_stabilize_cfg* cfg, double* quats) {
+    DeviceGuard dev_guard(c);
+    if (!cfg || !(cfg->sigma >= 0.0) || !std::isfinite(cfg->sigma)) return set_err(c, "stabilize: bad configuration");
+    if (c->n_knots < 2 || !c->coef64.p || cfg->n_knots != c->n_knots) return set_err(c, "stabilize: the device holds no spline table of the gyro data");
+    if (!n) return 0;
+    if (!frame_times || !quats) return set_err(c, "stabilize: null pointer");
+    if (n > 0x7fffffffu) return set_err(c, "stabilize: too many frames");
+    bool on_dev = false;
+    if (rect_pointer(c, quats, "the path's orientations", &on_dev, "stabilize")) return 1;
+    if (ensure(c, c->rect_times, n * 8)) return 1;
+    RS_HIP(hipMemcpy(c->rect_times.p, frame_times, n * 8, hipMemcpyHostToDevice));
+    if (stab_fill_targets(c, cfg, nullptr, n)) return 1;
+    RS_HIP(hipMemcpyAsync(quats, c->stab_targets.p, n * 32, hipMemcpyDefault, c->stream));
+    return sync_stream(c);
+}
+
+int rship_stabilize_frames(rship_ctx* c, const uint8_t* frames, uint32_t n_frames, size_t pitch, size_t frame_stride,
+                           const double* frame_times, const double* targets, const rship_stabilize_cfg* cfg, uint8_t* out,
+                           size_t out_pitch, size_t out_stride, uint64_t* n_outside, size_t budget_bytes) {
+    DeviceGuard dev_guard(c);
+    if (stab_check(c, cfg)) return 1;
+    return stab_frames_run(c, frames, n_frames, pitch, frame_stride, frame_times, targets, cfg, out, out_pitch, out_stride, n_outside, budget_bytes,
+                           true, [&](const StabArgs& A, uint32_t, uint32_t cnt) { stab_launch<false>(c, cfg, A, cnt); });
 }
 
 int rship_stabilize_map(rship_ctx* c, double frame_time, const double* target, const rship_stabilize_cfg* cfg, float* map_xy) {
@@ -4201,6 +4217,101 @@ int rship_stabilize_coverage(rship_ctx* c, const double* frame_times, uint32_t n
     }
     RS_HIP(hipMemcpyAsync(outside, c->stab_cover.p, counts, hipMemcpyDeviceToHost, c->stream));
     return sync_stream(c);
+}
+
+} // extern "C"
+
+// ===========================================================================
+// dynamic zoom (kernels/zoom.hpp; declared in zoom_hip.h, called by zoom_api.cpp).  The stabiliser's plumbing: the fit is
+// the coverage sweep's pipeline with one workgroup per frame, the render is the frames' pipeline with a camera per frame.
+
+extern "C" {
+
+int rship_zoom_fit(rship_ctx* c, const double* frame_times, uint32_t n_frames, const double* targets, const rship_stabilize_cfg* cfg,
+                   double lo, double hi, int32_t steps, double* zooms, uint32_t* status) {
+    DeviceGuard dev_guard(c);
+    if (stab_check(c, cfg)) return 1;
+    if (!(lo > 0.0 && lo < hi) || !std::isfinite(hi) || steps < 1 || steps > rs::kZoomMaxSteps) return set_err(c, "zoom: bad range or steps");
+    if (!n_frames) return 0;
+    if (!frame_times || !zooms) return set_err(c, "zoom: null pointer");
+    const uint32_t h = cfg->height, ow = cfg->out_width, oh = cfg->out_height;
+    const size_t tab = (size_t)(h + 1) * 9 * sizeof(float);
+    const uint32_t chunk = (uint32_t)std::min<uint64_t>(std::min(n_frames, 65535u), std::max<uint64_t>(1, kStabCoverTables / tab));
+    // (the sweep's buffers: its zooms hold the results, its counts the statuses)
+    if (ensure(c, c->rect_slot[0], (size_t)chunk * tab) || ensure(c, c->rect_times, (size_t)n_frames * 8) ||
+        ensure(c, c->stab_zooms, (size_t)n_frames * 8) || ensure(c, c->stab_cover, (size_t)n_frames * sizeof(uint32_t)))
+        return 1;
+    RS_HIP(hipMemcpy(c->rect_times.p, frame_times, (size_t)n_frames * 8, hipMemcpyHostToDevice));
+    if (stab_fill_targets(c, cfg, targets, n_frames)) return 1;
+    StabRowsArgs R = stab_rows_args(c, cfg);
+    R.rows_tab = (float*)c->rect_slot[0].p;
+    ZoomFitArgs Z{};
+    Z.rows_tab = (const float*)c->rect_slot[0].p;
+    Z.cam = rs::Lens{0.0, cfg->cam[0], cfg->cam[1], cfg->cam[2], cfg->cam[3], cfg->lens[5], cfg->lens[6], cfg->lens[7], cfg->lens[8]};
+    Z.lens = stab_lens_f(cfg);
+    Z.lo = lo;
+    Z.hi = hi;
+    Z.y_scale = (float)cfg->height / (float)cfg->out_height;
+    Z.width = cfg->width;
+    Z.height = h;
+    Z.out_width = ow;
+    Z.out_height = oh;
+    Z.n_border = 2 * (ow + oh) - 4;
+    Z.iterations = cfg->iterations;
+    Z.camera = cfg->camera;
+    Z.steps = steps;
+    // every step on the one stream (a step's tables are read before the next step's rows kernel overwrites them), one wait
+    for (uint32_t f0 = 0; f0 < n_frames; f0 += chunk) {
+        const uint32_t cnt = std::min(chunk, n_frames - f0);
+        R.times = (const double*)c->rect_times.p + f0;
+        R.targets = (const double*)c->stab_targets.p + (size_t)f0 * 4;
+        R.n_frames = cnt;
+        hipLaunchKernelGGL(stabilize_rows_kernel, dim3((h + 1 + 255) / 256, cnt), dim3(256), 0, c->stream, R);
+        RS_HIP(hipGetLastError());
+        Z.zooms = (double*)c->stab_zooms.p + f0;
+        Z.status = (uint32_t*)c->stab_cover.p + f0;
+        hipLaunchKernelGGL(zoom_fit_kernel, dim3(cnt), dim3(256), 0, c->stream, Z);
+        RS_HIP(hipGetLastError());
+    }
+    RS_HIP(hipMemcpyAsync(zooms, c->stab_zooms.p, (size_t)n_frames * 8, hipMemcpyDeviceToHost, c->stream));
+    if (status) RS_HIP(hipMemcpyAsync(status, c->stab_cover.p, (size_t)n_frames * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    return sync_stream(c);
+}
+
+int rship_zoom_frames(rship_ctx* c, const uint8_t* frames, uint32_t n_frames, size_t pitch, size_t frame_stride,
+                      const double* frame_times, const double* targets, const rship_stabilize_cfg* cfg, const double* zooms, uint8_t* out,
+                      size_t out_pitch, size_t out_stride, uint64_t* n_outside, size_t budget_bytes) {
+    DeviceGuard dev_guard(c);
+    if (stab_check(c, cfg)) return 1;
+    if (!zooms) return set_err(c, "zoom: null pointer");
+    // the cameras of all frames: (fx zoom, fy zoom), fp64 products as the stabiliser's configuration holds them
+    std::vector<double> cams((size_t)n_frames * 2);
+    for (uint32_t f = 0; f < n_frames; ++f) {
+        if (!(zooms[f] > 0.0) || !std::isfinite(zooms[f])) return set_err(c, "zoom: every zoom must be finite and > 0");
+        cams[2 * (size_t)f] = cfg->cam[0] * zooms[f];
+        cams[2 * (size_t)f + 1] = cfg->cam[1] * zooms[f];
+    }
+    if (n_frames) {
+        if (ensure(c, c->stab_zooms, cams.size() * 8)) return 1;
+        RS_HIP(hipMemcpy(c->stab_zooms.p, cams.data(), cams.size() * 8, hipMemcpyHostToDevice));
+    }
+    ZoomRenderArgs Z{};
+    Z.cx = cfg->cam[2];
+    Z.cy = cfg->cam[3];
+    Z.k1 = cfg->lens[5];
+    Z.k2 = cfg->lens[6];
+    Z.k3 = cfg->lens[7];
+    Z.k4 = cfg->lens[8];
+    return stab_frames_run(c, frames, n_frames, pitch, frame_stride, frame_times, targets, cfg, out, out_pitch, out_stride, n_outside, budget_bytes,
+                           false, [&](const StabArgs& A, uint32_t f0, uint32_t cnt) {
+                               Z.S = A;
+                               Z.cams = (const double*)c->stab_zooms.p + 2 * (size_t)f0;
+                               const dim3 grid((cfg->out_width + kRectTW - 1) / kRectTW, (cfg->out_height + kRectTH - 1) / kRectTH, cnt);
+                               if (cfg->camera == 0 && cfg->filter == 0) hipLaunchKernelGGL((zoom_render_kernel<0, 0>), grid, dim3(256), 0, c->stream, Z);
+                               else if (cfg->camera == 0) hipLaunchKernelGGL((zoom_render_kernel<0, 1>), grid, dim3(256), 0, c->stream, Z);
+                               else if (cfg->filter == 0) hipLaunchKernelGGL((zoom_render_kernel<1, 0>), grid, dim3(256), 0, c->stream, Z);
+                               else hipLaunchKernelGGL((zoom_render_kernel<1, 1>), grid, dim3(256), 0, c->stream, Z);
+                           });
 }
 
 } // extern "C"

@@ -715,6 +715,34 @@ class SyncProblem:
         from . import stabilize
         return stabilize.stabilize_zoom(self, width, height, lens, frame_times, delay, zooms, **params)
 
+    def fit_zoom(self, width, height, lens, frame_times, delay, lo, hi, **params):
+        """-> (zooms (n,), status (n,)): every frame's smallest zoom in [lo, hi] that keeps the output's borders inside the
+        frame, found by a bisection on the device (include/rssync_zoom.h, rssync_amd.zoom).  params: steps, targets,
+        out_size, sigma, camera, out_camera, iterations."""
+        from . import zoom
+        return zoom.fit_zoom(self, width, height, lens, frame_times, delay, lo, hi, **params)
+
+    def smooth_zooms(self, frame_times, zooms, window):
+        """-> (n,): the envelope of a fitted zoom curve over `window` seconds, never below the curve."""
+        from . import zoom
+        return zoom.smooth_zooms(self, frame_times, zooms, window)
+
+    def dynamic_zoom(self, width, height, lens, frame_times, delay, lo, hi, window, **params):
+        """-> (n,): fit_zoom followed by smooth_zooms; raises where a frame is not clear at `hi`."""
+        from . import zoom
+        return zoom.dynamic_zoom(self, width, height, lens, frame_times, delay, lo, hi, window, **params)
+
+    def stabilize_frames_zoomed(self, frames, frame_times, lens, delay, zooms, **params):
+        """stabilize_frames with one zoom per frame -> (frames (n, out_height, out_width), n_outside (n,)).  params:
+        targets, out_size, out, sigma, camera, out_camera, iterations, fill, filter."""
+        from . import zoom
+        return zoom.stabilize_frames_zoomed(self, frames, frame_times, lens, delay, zooms, **params)
+
+    def stabilize_frames_zoomed_budget(self, frames, frame_times, lens, delay, zooms, budget_bytes, **params):
+        """stabilize_frames_zoomed through the internal launcher with a device budget for its chunk slots (tests)."""
+        from . import zoom
+        return zoom.stabilize_frames_zoomed_budget(self, frames, frame_times, lens, delay, zooms, budget_bytes, **params)
+
     def stabilize_color(self, fmt, frames, frame_times, lens, delay, **params):
         """Colour frames (rssync_amd.color: GRAY8, NV12, I420, RGBA32, and with uint16 samples GRAY16, P010, P016, I010)
         rendered at the smoothed path's orientations, or at `targets`, all planes of a frame in one pass
