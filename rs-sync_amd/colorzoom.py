@@ -1,0 +1,162 @@
+"""The dynamic zoom for colour video (include/rssync_colorzoom.h): one zoom per frame for every format of rssync_amd.color.
+
+``stabilize_color_zoomed`` renders every frame at its own zoom, byte for byte what ``stabilize_color(zoom=...)`` gives for
+that frame alone, in every plane (csrc/kernels/colorzoom.hpp).  ``fit_zoom_color`` finds every frame's smallest zoom that
+clears all planes: the larger of ``fit_zoom`` on the luma plane and ``fit_zoom`` on the 4:2:0 chroma plane, which is the
+image of a camera of its own with a border of its own.  ``dynamic_zoom_color`` is that fit followed by ``smooth_zooms``.
+
+Frames and results are those of ``stabilize_color``.
+
+Its own ctypes table, bound to the product library only, like rssync_amd.color.
+"""
+import ctypes as C
+
+import numpy as np
+
+from .color import (CHROMA_CENTER, DEPTH, I420, NV12, RGBA32, SIBLING, ColorParams, _Cfg, _as_planes, _image, _out_like, _size,
+                    chroma_config, params, plane_shapes)
+from .color import ColorImage
+from .problem import RsSyncError, load_library
+from .rectify import _check, _lens
+from .stabilize import CAMERA_LENS, DEFAULT_ITERATIONS, FILTER_BILINEAR, _Cfg as _StabCfg, _targets, _times
+from .zoom import _zooms, smooth_zooms
+
+_PD = C.POINTER(C.c_double)
+_PI = C.POINTER(ColorImage)
+_PP = C.POINTER(ColorParams)
+_PU32 = C.POINTER(C.c_uint32)
+_PU64 = C.POINTER(C.c_uint64)
+_SZ = C.c_size_t
+
+# name -> (restype, argtypes): every function include/rssync_colorzoom.h declares, and the internal launcher the tests call
+SIGNATURES = {
+    "rssync_colorzoom_stabilize": (C.c_int, [C.c_void_p, C.c_int, _PI, _SZ, _SZ, _SZ, _PD, C.c_void_p, C.c_double, _PD, _PP, _PI, _SZ, _SZ,
+                                             _PU64, _PD]),
+    "rssync_colorzoom_fit": (C.c_int, [C.c_void_p, C.c_int, _SZ, _SZ, C.c_void_p, _SZ, _SZ, _PD, _SZ, C.c_double, _PD, _PP, C.c_double,
+                                       C.c_double, C.c_int32, _PD, _PU32]),
+    "rship_colorzoom_frames": (C.c_int, [C.c_void_p, _PI, C.c_uint32, _PD, _PD, C.POINTER(_Cfg), _PD, _PI, _PU64, _SZ]),
+    "rship_last_error": (C.c_char_p, [C.c_void_p]),
+}
+
+_BOUND = None
+
+
+def library():
+    """the product library with the colour dynamic zoom's signatures attached"""
+    global _BOUND
+    lib = load_library()
+    if _BOUND is not lib:
+        for name, (res, args) in SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        _BOUND = lib
+    return lib
+
+
+def _lib_of(problem):
+    lib = library()
+    if problem._lib is not lib:
+        raise RsSyncError("the colour dynamic zoom runs in the product library only")
+    return lib
+
+
+def stabilize_color_zoomed(problem, fmt, frames, frame_times, lens, delay, zooms, targets=None, out_size=None, out=None,
+                           chroma_site=CHROMA_CENTER, fills=None, **kw):
+    """stabilize_color with zooms[f] for frame f -> (stabilised frames in the layout of `frames` -- `out` if given --,
+    n_outside (n, 2) uint64).  kw: sigma, camera, out_camera, iterations, fill, filter."""
+    lib = _lib_of(problem)
+    planes = _as_planes(fmt, frames)
+    n, h, w = _size(fmt, planes)
+    src, keep = _image(fmt, planes, n, h, w, False)
+    t = _times(frame_times, n)
+    z = _zooms(zooms, n)
+    L = _lens(lens)
+    ow, oh = (w, h) if out_size is None else (int(out_size[0]), int(out_size[1]))
+    res = _out_like(fmt, planes, n, oh, ow) if out is None else _as_planes(fmt, out)
+    dst, okeep = _image(fmt, res, n, oh, ow, True)
+    prm = params(chroma_site, fills, **kw)
+    tptr, tkeep = _targets(targets, n)
+    outside = np.zeros((max(n, 1), 2), np.uint64)
+    _check(problem, lib.rssync_colorzoom_stabilize(problem._h, int(fmt), C.byref(src), n, w, h, t.ctypes.data_as(_PD), L.ctypes.data,
+                                                   float(delay), tptr, C.byref(prm), C.byref(dst), ow, oh, outside.ctypes.data_as(_PU64),
+                                                   z.ctypes.data_as(_PD)))
+    del keep, okeep, tkeep
+    if out is not None:
+        return out, outside[:n]
+    return (res[0] if len(res) == 1 else tuple(res)), outside[:n]
+
+
+def stabilize_color_zoomed_budget(problem, fmt, frames, frame_times, lens, delay, zooms, budget_bytes, out_size=None, sigma=0.0,
+                                  chroma_site=CHROMA_CENTER, camera=CAMERA_LENS, iterations=DEFAULT_ITERATIONS, fills=None,
+                                  filter=FILTER_BILINEAR):
+    """stabilize_color_zoomed along the path through the internal launcher with its device budget for the chunk slots given
+    (tests: small frames that span several chunks).  fills: None = the header's defaults for fill 0.
+    numpy frames -> (planes, n_outside (n, 2))"""
+    lib = _lib_of(problem)
+    if fills is None:
+        fills = (0, 0, 0, 255) if fmt == RGBA32 else (0, 128 << (DEPTH.get(fmt, 8) - 8), 128 << (DEPTH.get(fmt, 8) - 8), 0)
+    planes = _as_planes(fmt, frames)
+    n, h, w = _size(fmt, planes)
+    src, keep = _image(fmt, planes, n, h, w, False)
+    t = _times(frame_times, n)
+    z = _zooms(zooms, n)
+    L = _lens(lens)
+    ow, oh = (w, h) if out_size is None else (int(out_size[0]), int(out_size[1]))
+    fs, start, n_knots = problem.gyro_info()
+    sx, sy = ow / w, oh / h
+    cam = (L[1] * sx, L[2] * sy, L[3] * sx, L[4] * sy)      # (at zoom 1: the launcher multiplies)
+
+    def stab_cfg(w_, h_, ow_, oh_, lens_, cam_):
+        return _StabCfg(w_, h_, ow_, oh_, (C.c_double * 9)(*lens_), (C.c_double * 4)(*cam_), start, fs, n_knots, float(delay), float(sigma),
+                        int(camera), int(iterations), 0 if fmt in SIBLING else int(fills[0]), int(filter))
+
+    cfg = _Cfg()
+    cfg.luma = stab_cfg(w, h, ow, oh, L, cam)
+    cfg.chroma = cfg.luma
+    if SIBLING.get(fmt, fmt) in (NV12, I420):
+        lens_c, cam_c, cfg.chroma_time = chroma_config(L, w, h, ow, oh, chroma_site)
+        cfg.chroma = stab_cfg(w // 2, h // 2, ow // 2, oh // 2, lens_c, cam_c)
+    cfg.format = int(fmt)
+    for k in range(4):
+        cfg.fill[k] = int(fills[k])
+    res = [np.empty(s, np.uint16 if fmt in SIBLING else np.uint8) for s in plane_shapes(fmt, n, oh, ow)]
+    dst, okeep = _image(fmt, res, n, oh, ow, True)
+    outside = np.zeros((max(n, 1), 2), np.uint64)
+    ctx = C.c_void_p(problem.device_context())
+    if lib.rship_colorzoom_frames(ctx, C.byref(src), n, t.ctypes.data_as(_PD), None, C.byref(cfg), z.ctypes.data_as(_PD), C.byref(dst),
+                                  outside.ctypes.data_as(_PU64), int(budget_bytes)):
+        raise RsSyncError(lib.rship_last_error(ctx).decode())
+    del keep, okeep
+    return (res[0] if len(res) == 1 else tuple(res)), outside[:n]
+
+
+def fit_zoom_color(problem, fmt, width, height, lens, frame_times, delay, lo, hi, steps=0, targets=None, out_size=None,
+                   chroma_site=CHROMA_CENTER, **kw):
+    """-> (zooms (n,) float64, status (n,) uint32): per frame the smallest zoom in [lo, hi] at which no border sample of any
+    plane of the output sees past its plane of the frame: the maximum of fit_zoom on plane 0 and, for the 4:2:0 formats,
+    fit_zoom on the chroma plane as a camera of its own; the statuses OR-ed.  kw: sigma, camera, out_camera, iterations."""
+    lib = _lib_of(problem)
+    L = _lens(lens)
+    t = _times(frame_times)
+    n = t.shape[0]
+    ow, oh = (int(width), int(height)) if out_size is None else (int(out_size[0]), int(out_size[1]))
+    prm = params(chroma_site, None, **kw)
+    tptr, tkeep = _targets(targets, n)
+    zooms = np.zeros(n, np.float64)
+    status = np.zeros(n, np.uint32)
+    _check(problem, lib.rssync_colorzoom_fit(problem._h, int(fmt), int(width), int(height), L.ctypes.data, ow, oh, t.ctypes.data_as(_PD), n,
+                                             float(delay), tptr, C.byref(prm), float(lo), float(hi), int(steps),
+                                             zooms.ctypes.data_as(_PD), status.ctypes.data_as(_PU32)))
+    del tkeep
+    return zooms, status
+
+
+def dynamic_zoom_color(problem, fmt, width, height, lens, frame_times, delay, lo, hi, window, steps=0, targets=None, out_size=None,
+                       chroma_site=CHROMA_CENTER, **kw):
+    """-> (n,) float64: fit_zoom_color followed by smooth_zooms.  Raises where a frame is not clear at `hi`."""
+    zooms, status = fit_zoom_color(problem, fmt, width, height, lens, frame_times, delay, lo, hi, steps=steps, targets=targets,
+                                   out_size=out_size, chroma_site=chroma_site, **kw)
+    if status.any():
+        raise RsSyncError("dynamic zoom: frames %s are not clear at the largest zoom %g" % (np.flatnonzero(status).tolist(), hi))
+    return smooth_zooms(problem, frame_times, zooms, window)

@@ -59,6 +59,7 @@
 #include "stabilize_hip.h"
 #include "color_hip.h"
 #include "zoom_hip.h"
+#include "colorzoom_hip.h"
 #include "device_math.hpp"
 #include "sync_math.hpp"
 #include "lens_math.hpp"
@@ -95,6 +96,7 @@ using rs::f4;
 #include "kernels/color16.hpp"
 #include "kernels/resample.hpp"
 #include "kernels/zoom.hpp"
+#include "kernels/colorzoom.hpp"
 
 // ===========================================================================
 // host side of the C-ABI
@@ -4386,14 +4388,21 @@ ColorCam color_cam(const rship_stabilize_cfg* g, const float4* rays) {
     return C;
 }
 
-} // namespace
+// what a chunk's render launch gets besides the chunk: the colour kernels' arguments, GRAY8's (the stabiliser's kernel), and
+// the 16-bit kernels' fills as stored words
+struct ColorLaunch {
+    ColorArgs A;
+    StabArgs G;
+    uint32_t fill16_y, fill16_uv;
+};
 
-extern "C" {
-
-int rship_color_frames(rship_ctx* c, const rship_color_image* in, uint32_t n_frames, const double* frame_times, const double* targets,
-                       const rship_color_cfg* cfg, const rship_color_image* out, uint64_t* n_outside, size_t budget_bytes) {
-    DeviceGuard dev_guard(c);
-    if (color_check(c, cfg)) return 1;
+// The chunk pipeline of the colour frames: rship_color_frames' and rship_colorzoom_frames'.  launch(K, f0, cnt) enqueues the
+// kernel that renders the chunk's cnt frames, the first of which is frame f0 of the call; ray_maps: the cached ray maps of
+// cfg's output cameras are needed.
+template <class Launch>
+int color_frames_run(rship_ctx* c, const rship_color_image* in, uint32_t n_frames, const double* frame_times, const double* targets,
+                     const rship_color_cfg* cfg, const rship_color_image* out, uint64_t* n_outside, size_t budget_bytes, bool ray_maps,
+                     Launch&& launch) {
     if (!in || !out || !frame_times) return set_err(c, "color: null pointer");
     if (!n_frames) return 0;
     rship_stabilize_cfg L = cfg->luma;
@@ -4440,7 +4449,7 @@ int rship_color_frames(rship_ctx* c, const rship_color_image* in, uint32_t n_fra
     }
     RS_HIP(hipMemcpy(c->rect_times.p, times.data(), times.size() * 8, hipMemcpyHostToDevice));
     RS_HIP(hipMemsetAsync(c->rect_count.p, 0, (size_t)n_frames * 16, c->stream));
-    if (stab_fill_targets(c, &L, targets, n_frames) || stab_rays(c, &L) || (yuv && stab_rays(c, &cfg->chroma, true))) return 1;
+    if (stab_fill_targets(c, &L, targets, n_frames) || (ray_maps && (stab_rays(c, &L) || (yuv && stab_rays(c, &cfg->chroma, true))))) return 1;
     ColorRowsArgs R{};
     R.table = (const double*)c->coef64.p;
     R.start = L.start;
@@ -4450,8 +4459,10 @@ int rship_color_frames(rship_ctx* c, const rship_color_image* in, uint32_t n_fra
     R.n_knots = c->n_knots;
     R.rows = h;
     R.rows_c = hc;
-    StabArgs G = stab_args(c, &L); // GRAY8: the stabiliser's kernel
-    ColorArgs A{};
+    ColorLaunch K{};
+    StabArgs& G = K.G;
+    G = stab_args(c, &L); // GRAY8: the stabiliser's kernel
+    ColorArgs& A = K.A;
     A.luma = color_cam(&L, (const float4*)c->rect_rays.p);
     if (yuv) A.chroma = color_cam(&cfg->chroma, (const float4*)c->rect_rays_c.p);
     A.width = L.width;
@@ -4462,7 +4473,8 @@ int rship_color_frames(rship_ctx* c, const rship_color_image* in, uint32_t n_fra
     A.fill = (uint32_t)cfg->fill[0] | (uint32_t)cfg->fill[1] << 8 | (uint32_t)cfg->fill[2] << 16 | (uint32_t)cfg->fill[3] << 24;
     // the 16-bit kernels' fills as stored words: P010's values sit in the ten high bits
     const uint32_t sh16 = cfg->format == 17 ? 6 : 0;
-    const uint32_t fill16_y = (uint32_t)cfg->fill[0] << sh16, fill16_uv = (uint32_t)cfg->fill[1] << sh16 | (uint32_t)cfg->fill[2] << (16 + sh16);
+    K.fill16_y = (uint32_t)cfg->fill[0] << sh16;
+    K.fill16_uv = (uint32_t)cfg->fill[1] << sh16 | (uint32_t)cfg->fill[2] << (16 + sh16);
     if (wide) A.fill = 0;
     // the chunk pipeline of rship_rectify_frames: chunk j in slot j & 1, uploads and downloads on the copy stream
     auto upload = [&](int slot, bool reused, uint32_t f0, uint32_t cnt) -> int {
@@ -4499,60 +4511,13 @@ int rship_color_frames(rship_ctx* c, const rship_color_image* in, uint32_t n_fra
             if (dev_out) { A.dst[k] = out->plane[k] + (size_t)f0 * out->stride[k]; A.dst_pitch[k] = out->pitch[k]; A.dst_stride[k] = out->stride[k]; }
             else { A.dst[k] = base + off_out[k]; A.dst_pitch[k] = po[k].row_bytes; A.dst_stride[k] = po[k].row_bytes * po[k].rows; }
         }
-        const dim3 grid((ow + kRectTW - 1) / kRectTW, (oh + kRectTH - 1) / kRectTH, cnt);
-        const dim3 grid_c((ow / 2 + kRectTW - 1) / kRectTW, (oh / 2 + kRectTH - 1) / kRectTH, cnt);
-        const bool lens_cam = L.camera == 0, cubic = L.filter == 1; // cubic: the siblings of kernels/resample.hpp
-        switch (cfg->format) {
-        case 0:
+        if (cfg->format == 0) {
             G.rows_tab = A.luma.rows_tab;
             G.outside = A.outside;
             G.src = A.src[0]; G.src_pitch = A.src_pitch[0]; G.src_stride = A.src_stride[0];
             G.dst = A.dst[0]; G.dst_pitch = A.dst_pitch[0]; G.dst_stride = A.dst_stride[0];
-            stab_launch<false>(c, &L, G, cnt);
-            break;
-        case 1:
-            if (cubic && lens_cam) hipLaunchKernelGGL((bicubic_yuv_kernel<0, true>), grid_c, dim3(256), 0, c->stream, A);
-            else if (cubic) hipLaunchKernelGGL((bicubic_yuv_kernel<1, true>), grid_c, dim3(256), 0, c->stream, A);
-            else if (lens_cam) hipLaunchKernelGGL((color_yuv_kernel<0, true>), grid_c, dim3(256), 0, c->stream, A);
-            else hipLaunchKernelGGL((color_yuv_kernel<1, true>), grid_c, dim3(256), 0, c->stream, A);
-            break;
-        case 2:
-            if (cubic && lens_cam) hipLaunchKernelGGL((bicubic_yuv_kernel<0, false>), grid_c, dim3(256), 0, c->stream, A);
-            else if (cubic) hipLaunchKernelGGL((bicubic_yuv_kernel<1, false>), grid_c, dim3(256), 0, c->stream, A);
-            else if (lens_cam) hipLaunchKernelGGL((color_yuv_kernel<0, false>), grid_c, dim3(256), 0, c->stream, A);
-            else hipLaunchKernelGGL((color_yuv_kernel<1, false>), grid_c, dim3(256), 0, c->stream, A);
-            break;
-        case 3:
-            if (cubic && lens_cam) hipLaunchKernelGGL((bicubic_rgba_kernel<0>), grid, dim3(256), 0, c->stream, A);
-            else if (cubic) hipLaunchKernelGGL((bicubic_rgba_kernel<1>), grid, dim3(256), 0, c->stream, A);
-            else if (lens_cam) hipLaunchKernelGGL((color_rgba_kernel<0>), grid, dim3(256), 0, c->stream, A);
-            else hipLaunchKernelGGL((color_rgba_kernel<1>), grid, dim3(256), 0, c->stream, A);
-            break;
-        case 16:
-            if (cubic && lens_cam) hipLaunchKernelGGL((bicubic16_gray_kernel<0>), grid, dim3(256), 0, c->stream, A, fill16_y);
-            else if (cubic) hipLaunchKernelGGL((bicubic16_gray_kernel<1>), grid, dim3(256), 0, c->stream, A, fill16_y);
-            else if (lens_cam) hipLaunchKernelGGL((color16_gray_kernel<0>), grid, dim3(256), 0, c->stream, A, fill16_y);
-            else hipLaunchKernelGGL((color16_gray_kernel<1>), grid, dim3(256), 0, c->stream, A, fill16_y);
-            break;
-        case 17:
-            if (cubic && lens_cam) hipLaunchKernelGGL((bicubic16_yuv_kernel<0, true, 6>), grid_c, dim3(256), 0, c->stream, A, fill16_y, fill16_uv);
-            else if (cubic) hipLaunchKernelGGL((bicubic16_yuv_kernel<1, true, 6>), grid_c, dim3(256), 0, c->stream, A, fill16_y, fill16_uv);
-            else if (lens_cam) hipLaunchKernelGGL((color16_yuv_kernel<0, true, 6>), grid_c, dim3(256), 0, c->stream, A, fill16_y, fill16_uv);
-            else hipLaunchKernelGGL((color16_yuv_kernel<1, true, 6>), grid_c, dim3(256), 0, c->stream, A, fill16_y, fill16_uv);
-            break;
-        case 18:
-            if (cubic && lens_cam) hipLaunchKernelGGL((bicubic16_yuv_kernel<0, true, 0>), grid_c, dim3(256), 0, c->stream, A, fill16_y, fill16_uv);
-            else if (cubic) hipLaunchKernelGGL((bicubic16_yuv_kernel<1, true, 0>), grid_c, dim3(256), 0, c->stream, A, fill16_y, fill16_uv);
-            else if (lens_cam) hipLaunchKernelGGL((color16_yuv_kernel<0, true, 0>), grid_c, dim3(256), 0, c->stream, A, fill16_y, fill16_uv);
-            else hipLaunchKernelGGL((color16_yuv_kernel<1, true, 0>), grid_c, dim3(256), 0, c->stream, A, fill16_y, fill16_uv);
-            break;
-        case 19:
-            if (cubic && lens_cam) hipLaunchKernelGGL((bicubic16_yuv_kernel<0, false, 0>), grid_c, dim3(256), 0, c->stream, A, fill16_y, fill16_uv);
-            else if (cubic) hipLaunchKernelGGL((bicubic16_yuv_kernel<1, false, 0>), grid_c, dim3(256), 0, c->stream, A, fill16_y, fill16_uv);
-            else if (lens_cam) hipLaunchKernelGGL((color16_yuv_kernel<0, false, 0>), grid_c, dim3(256), 0, c->stream, A, fill16_y, fill16_uv);
-            else hipLaunchKernelGGL((color16_yuv_kernel<1, false, 0>), grid_c, dim3(256), 0, c->stream, A, fill16_y, fill16_uv);
-            break;
         }
+        launch(K, f0, cnt);
         RS_HIP(hipGetLastError());
         RS_HIP(hipEventRecord(c->trk_k[slot], c->stream));
         used[slot] = true;
@@ -4577,6 +4542,73 @@ int rship_color_frames(rship_ctx* c, const rship_color_image* in, uint32_t n_fra
         n_outside[2 * k + 1] = counts[n_frames + k];
     }
     return 0;
+}
+
+} // namespace
+
+extern "C" {
+
+int rship_color_frames(rship_ctx* c, const rship_color_image* in, uint32_t n_frames, const double* frame_times, const double* targets,
+                       const rship_color_cfg* cfg, const rship_color_image* out, uint64_t* n_outside, size_t budget_bytes) {
+    DeviceGuard dev_guard(c);
+    if (color_check(c, cfg)) return 1;
+    rship_stabilize_cfg L = cfg->luma;
+    if (!color_is_16(cfg->format)) L.fill = cfg->fill[0];
+    const uint32_t ow = L.out_width, oh = L.out_height;
+    return color_frames_run(c, in, n_frames, frame_times, targets, cfg, out, n_outside, budget_bytes, true,
+                            [&](const ColorLaunch& K, uint32_t, uint32_t cnt) {
+        const ColorArgs& A = K.A;
+        const dim3 grid((ow + kRectTW - 1) / kRectTW, (oh + kRectTH - 1) / kRectTH, cnt);
+        const dim3 grid_c((ow / 2 + kRectTW - 1) / kRectTW, (oh / 2 + kRectTH - 1) / kRectTH, cnt);
+        const bool lens_cam = L.camera == 0, cubic = L.filter == 1; // cubic: the siblings of kernels/resample.hpp
+        switch (cfg->format) {
+        case 0:
+            stab_launch<false>(c, &L, K.G, cnt);
+            break;
+        case 1:
+            if (cubic && lens_cam) hipLaunchKernelGGL((bicubic_yuv_kernel<0, true>), grid_c, dim3(256), 0, c->stream, A);
+            else if (cubic) hipLaunchKernelGGL((bicubic_yuv_kernel<1, true>), grid_c, dim3(256), 0, c->stream, A);
+            else if (lens_cam) hipLaunchKernelGGL((color_yuv_kernel<0, true>), grid_c, dim3(256), 0, c->stream, A);
+            else hipLaunchKernelGGL((color_yuv_kernel<1, true>), grid_c, dim3(256), 0, c->stream, A);
+            break;
+        case 2:
+            if (cubic && lens_cam) hipLaunchKernelGGL((bicubic_yuv_kernel<0, false>), grid_c, dim3(256), 0, c->stream, A);
+            else if (cubic) hipLaunchKernelGGL((bicubic_yuv_kernel<1, false>), grid_c, dim3(256), 0, c->stream, A);
+            else if (lens_cam) hipLaunchKernelGGL((color_yuv_kernel<0, false>), grid_c, dim3(256), 0, c->stream, A);
+            else hipLaunchKernelGGL((color_yuv_kernel<1, false>), grid_c, dim3(256), 0, c->stream, A);
+            break;
+        case 3:
+            if (cubic && lens_cam) hipLaunchKernelGGL((bicubic_rgba_kernel<0>), grid, dim3(256), 0, c->stream, A);
+            else if (cubic) hipLaunchKernelGGL((bicubic_rgba_kernel<1>), grid, dim3(256), 0, c->stream, A);
+            else if (lens_cam) hipLaunchKernelGGL((color_rgba_kernel<0>), grid, dim3(256), 0, c->stream, A);
+            else hipLaunchKernelGGL((color_rgba_kernel<1>), grid, dim3(256), 0, c->stream, A);
+            break;
+        case 16:
+            if (cubic && lens_cam) hipLaunchKernelGGL((bicubic16_gray_kernel<0>), grid, dim3(256), 0, c->stream, A, K.fill16_y);
+            else if (cubic) hipLaunchKernelGGL((bicubic16_gray_kernel<1>), grid, dim3(256), 0, c->stream, A, K.fill16_y);
+            else if (lens_cam) hipLaunchKernelGGL((color16_gray_kernel<0>), grid, dim3(256), 0, c->stream, A, K.fill16_y);
+            else hipLaunchKernelGGL((color16_gray_kernel<1>), grid, dim3(256), 0, c->stream, A, K.fill16_y);
+            break;
+        case 17:
+            if (cubic && lens_cam) hipLaunchKernelGGL((bicubic16_yuv_kernel<0, true, 6>), grid_c, dim3(256), 0, c->stream, A, K.fill16_y, K.fill16_uv);
+            else if (cubic) hipLaunchKernelGGL((bicubic16_yuv_kernel<1, true, 6>), grid_c, dim3(256), 0, c->stream, A, K.fill16_y, K.fill16_uv);
+            else if (lens_cam) hipLaunchKernelGGL((color16_yuv_kernel<0, true, 6>), grid_c, dim3(256), 0, c->stream, A, K.fill16_y, K.fill16_uv);
+            else hipLaunchKernelGGL((color16_yuv_kernel<1, true, 6>), grid_c, dim3(256), 0, c->stream, A, K.fill16_y, K.fill16_uv);
+            break;
+        case 18:
+            if (cubic && lens_cam) hipLaunchKernelGGL((bicubic16_yuv_kernel<0, true, 0>), grid_c, dim3(256), 0, c->stream, A, K.fill16_y, K.fill16_uv);
+            else if (cubic) hipLaunchKernelGGL((bicubic16_yuv_kernel<1, true, 0>), grid_c, dim3(256), 0, c->stream, A, K.fill16_y, K.fill16_uv);
+            else if (lens_cam) hipLaunchKernelGGL((color16_yuv_kernel<0, true, 0>), grid_c, dim3(256), 0, c->stream, A, K.fill16_y, K.fill16_uv);
+            else hipLaunchKernelGGL((color16_yuv_kernel<1, true, 0>), grid_c, dim3(256), 0, c->stream, A, K.fill16_y, K.fill16_uv);
+            break;
+        case 19:
+            if (cubic && lens_cam) hipLaunchKernelGGL((bicubic16_yuv_kernel<0, false, 0>), grid_c, dim3(256), 0, c->stream, A, K.fill16_y, K.fill16_uv);
+            else if (cubic) hipLaunchKernelGGL((bicubic16_yuv_kernel<1, false, 0>), grid_c, dim3(256), 0, c->stream, A, K.fill16_y, K.fill16_uv);
+            else if (lens_cam) hipLaunchKernelGGL((color16_yuv_kernel<0, false, 0>), grid_c, dim3(256), 0, c->stream, A, K.fill16_y, K.fill16_uv);
+            else hipLaunchKernelGGL((color16_yuv_kernel<1, false, 0>), grid_c, dim3(256), 0, c->stream, A, K.fill16_y, K.fill16_uv);
+            break;
+        }
+    });
 }
 
 int rship_color_map(rship_ctx* c, int plane, double frame_time, const double* target, const rship_color_cfg* cfg, float* map_xy) {
@@ -4615,6 +4647,107 @@ int rship_color_map(rship_ctx* c, int plane, double frame_time, const double* ta
     RS_HIP(hipGetLastError());
     if (!on_dev) RS_HIP(hipMemcpyAsync(map_xy, c->rect_tmp.p, n * sizeof(float2), hipMemcpyDeviceToHost, c->stream));
     return sync_stream(c);
+}
+
+} // extern "C"
+
+// ===========================================================================
+// colour frames with one zoom per frame (kernels/colorzoom.hpp; declared in colorzoom_hip.h, called by colorzoom_api.cpp).
+// The colour front's pipeline with a camera per frame, as rship_zoom_frames is the stabiliser's.
+
+namespace {
+
+template <template <int, int> class Pick>
+void percam_launch2(rship_ctx* c, bool lens_cam, bool cubic, dim3 grid, const PercamArgs& P) {
+    if (lens_cam && !cubic) hipLaunchKernelGGL((Pick<0, 0>::kernel), grid, dim3(256), 0, c->stream, P);
+    else if (lens_cam) hipLaunchKernelGGL((Pick<0, 1>::kernel), grid, dim3(256), 0, c->stream, P);
+    else if (!cubic) hipLaunchKernelGGL((Pick<1, 0>::kernel), grid, dim3(256), 0, c->stream, P);
+    else hipLaunchKernelGGL((Pick<1, 1>::kernel), grid, dim3(256), 0, c->stream, P);
+}
+
+template <int C, int F> struct PercamNv12 { static constexpr auto kernel = percam_yuv8_kernel<C, true, F>; };
+template <int C, int F> struct PercamI420 { static constexpr auto kernel = percam_yuv8_kernel<C, false, F>; };
+template <int C, int F> struct PercamRgba { static constexpr auto kernel = percam_rgba8_kernel<C, F>; };
+template <int C, int F> struct PercamGray16 { static constexpr auto kernel = percam_gray16_kernel<C, F>; };
+template <int C, int F> struct PercamP010 { static constexpr auto kernel = percam_yuv16_kernel<C, true, 6, F>; };
+template <int C, int F> struct PercamP016 { static constexpr auto kernel = percam_yuv16_kernel<C, true, 0, F>; };
+template <int C, int F> struct PercamI010 { static constexpr auto kernel = percam_yuv16_kernel<C, false, 0, F>; };
+
+} // namespace
+
+extern "C" {
+
+int rship_colorzoom_frames(rship_ctx* c, const rship_color_image* in, uint32_t n_frames, const double* frame_times, const double* targets,
+                           const rship_color_cfg* cfg, const double* zooms, const rship_color_image* out, uint64_t* n_outside,
+                           size_t budget_bytes) {
+    DeviceGuard dev_guard(c);
+    if (color_check(c, cfg)) return 1;
+    if (!zooms) return set_err(c, "colorzoom: null pointer");
+    rship_stabilize_cfg L = cfg->luma;
+    if (!color_is_16(cfg->format)) L.fill = cfg->fill[0];
+    // the cameras of all frames, fp64 products as the colour front's configuration holds them for a constant zoom:
+    // luma (fx zoom, fy zoom), chroma the same times 0.5 (color_chroma_camera).  GRAY8: zoom_render_kernel's pairs
+    const size_t per = cfg->format == 0 ? 2 : 4;
+    std::vector<double> cams((size_t)n_frames * per);
+    for (uint32_t f = 0; f < n_frames; ++f) {
+        if (!(zooms[f] > 0.0) || !std::isfinite(zooms[f])) return set_err(c, "colorzoom: every zoom must be finite and > 0");
+        double* k = &cams[per * (size_t)f];
+        k[0] = L.cam[0] * zooms[f];
+        k[1] = L.cam[1] * zooms[f];
+        if (per == 4) {
+            k[2] = k[0] * 0.5;
+            k[3] = k[1] * 0.5;
+        }
+    }
+    if (n_frames) {
+        if (ensure(c, c->stab_zooms, cams.size() * 8)) return 1;
+        RS_HIP(hipMemcpy(c->stab_zooms.p, cams.data(), cams.size() * 8, hipMemcpyHostToDevice));
+    }
+    const uint32_t ow = L.out_width, oh = L.out_height;
+    PercamArgs P{};
+    P.cx = L.cam[2];
+    P.cy = L.cam[3];
+    P.cx_c = cfg->chroma.cam[2];
+    P.cy_c = cfg->chroma.cam[3];
+    P.k1 = L.lens[5];
+    P.k2 = L.lens[6];
+    P.k3 = L.lens[7];
+    P.k4 = L.lens[8];
+    ZoomRenderArgs Z{}; // GRAY8
+    Z.cx = P.cx;
+    Z.cy = P.cy;
+    Z.k1 = P.k1;
+    Z.k2 = P.k2;
+    Z.k3 = P.k3;
+    Z.k4 = P.k4;
+    return color_frames_run(c, in, n_frames, frame_times, targets, cfg, out, n_outside, budget_bytes, false,
+                            [&](const ColorLaunch& K, uint32_t f0, uint32_t cnt) {
+        const dim3 grid((ow + kRectTW - 1) / kRectTW, (oh + kRectTH - 1) / kRectTH, cnt);
+        const dim3 grid_c((ow / 2 + kRectTW - 1) / kRectTW, (oh / 2 + kRectTH - 1) / kRectTH, cnt);
+        const bool lens_cam = L.camera == 0, cubic = L.filter == 1;
+        if (cfg->format == 0) {
+            Z.S = K.G;
+            Z.cams = (const double*)c->stab_zooms.p + 2 * (size_t)f0;
+            if (lens_cam && !cubic) hipLaunchKernelGGL((zoom_render_kernel<0, 0>), grid, dim3(256), 0, c->stream, Z);
+            else if (lens_cam) hipLaunchKernelGGL((zoom_render_kernel<0, 1>), grid, dim3(256), 0, c->stream, Z);
+            else if (!cubic) hipLaunchKernelGGL((zoom_render_kernel<1, 0>), grid, dim3(256), 0, c->stream, Z);
+            else hipLaunchKernelGGL((zoom_render_kernel<1, 1>), grid, dim3(256), 0, c->stream, Z);
+            return;
+        }
+        P.C = K.A;
+        P.cams = (const double*)c->stab_zooms.p + 4 * (size_t)f0;
+        P.fill_y = K.fill16_y;
+        P.fill_uv = K.fill16_uv;
+        switch (cfg->format) {
+        case 1: percam_launch2<PercamNv12>(c, lens_cam, cubic, grid_c, P); break;
+        case 2: percam_launch2<PercamI420>(c, lens_cam, cubic, grid_c, P); break;
+        case 3: percam_launch2<PercamRgba>(c, lens_cam, cubic, grid, P); break;
+        case 16: percam_launch2<PercamGray16>(c, lens_cam, cubic, grid, P); break;
+        case 17: percam_launch2<PercamP010>(c, lens_cam, cubic, grid_c, P); break;
+        case 18: percam_launch2<PercamP016>(c, lens_cam, cubic, grid_c, P); break;
+        case 19: percam_launch2<PercamI010>(c, lens_cam, cubic, grid_c, P); break;
+        }
+    });
 }
 
 } // extern "C"

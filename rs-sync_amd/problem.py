@@ -759,6 +759,29 @@ class SyncProblem:
         from . import color
         return color.color_map(self, fmt, plane, width, height, lens, frame_time, delay, **params)
 
+    def stabilize_color_zoomed(self, fmt, frames, frame_times, lens, delay, zooms, **params):
+        """stabilize_color with one zoom per frame (include/rssync_colorzoom.h, rssync_amd.colorzoom) -> (frames in the layout
+        of `frames`, n_outside (n, 2)).  params: targets, out_size, out, chroma_site, fills, sigma, camera, out_camera,
+        iterations, fill, filter."""
+        from . import colorzoom
+        return colorzoom.stabilize_color_zoomed(self, fmt, frames, frame_times, lens, delay, zooms, **params)
+
+    def stabilize_color_zoomed_budget(self, fmt, frames, frame_times, lens, delay, zooms, budget_bytes, **params):
+        """stabilize_color_zoomed through the internal launcher with a device budget for its chunk slots (tests)."""
+        from . import colorzoom
+        return colorzoom.stabilize_color_zoomed_budget(self, fmt, frames, frame_times, lens, delay, zooms, budget_bytes, **params)
+
+    def fit_zoom_color(self, fmt, width, height, lens, frame_times, delay, lo, hi, **params):
+        """-> (zooms (n,), status (n,)): every frame's smallest zoom in [lo, hi] that clears every plane of the format, a
+        4:2:0 chroma plane included.  params: steps, targets, out_size, chroma_site, sigma, camera, out_camera, iterations."""
+        from . import colorzoom
+        return colorzoom.fit_zoom_color(self, fmt, width, height, lens, frame_times, delay, lo, hi, **params)
+
+    def dynamic_zoom_color(self, fmt, width, height, lens, frame_times, delay, lo, hi, window, **params):
+        """-> (n,): fit_zoom_color followed by smooth_zooms; raises where a frame is not clear at `hi`."""
+        from . import colorzoom
+        return colorzoom.dynamic_zoom_color(self, fmt, width, height, lens, frame_times, delay, lo, hi, window, **params)
+
     def device_context(self):
         """rship_ctx* of this problem (include/rssync_hip.h), for kernel-level tools."""
         return self._lib.rssync_ext_device_context(self._h)
