@@ -32,6 +32,8 @@
 //   *bicubic*_kernel   the siblings of the kernels that write pixels with the 4 x 4 Catmull-Rom sampler (kernels/resample.hpp).
 //   zoom_*_kernel      the dynamic zoom: every frame's smallest clear zoom by an in-kernel bisection, and the stabiliser's
 //                      warp with one output camera per frame (kernels/zoom.hpp).
+//   limit_fit_kernel   the path limiter: every frame's largest clear strength at a fixed zoom by an in-kernel bisection
+//                      that rebuilds the frame's row table for every candidate (kernels/limit.hpp).
 // Data layout and the roofline that bounds each kernel: DESIGN.md.
 // The kernels live in kernels/*.hpp (one header each, included below); this file holds the
 // device context and the launchers.
@@ -59,6 +61,7 @@
 #include "stabilize_hip.h"
 #include "color_hip.h"
 #include "zoom_hip.h"
+#include "limit_hip.h"
 #include "colorzoom_hip.h"
 #include "device_math.hpp"
 #include "sync_math.hpp"
@@ -68,6 +71,7 @@
 #include "color_math.hpp"
 #include "resample_math.hpp"
 #include "zoom_math.hpp"
+#include "limit_math.hpp"
 #include "gyro_math.hpp"
 #include "gyro_signal_math.hpp"
 #include "window_plan.hpp"
@@ -96,6 +100,7 @@ using rs::f4;
 #include "kernels/color16.hpp"
 #include "kernels/resample.hpp"
 #include "kernels/zoom.hpp"
+#include "kernels/limit.hpp"
 #include "kernels/colorzoom.hpp"
 
 // ===========================================================================
@@ -168,6 +173,9 @@ struct rship_ctx {
     // colour front (rship_color_*): shares all of the above; its own is a second cached ray map, the chroma output camera's,
     // keyed as the first is, so that a 4:2:0 call of one configuration after another computes neither
     DevBuf rect_rays_c;
+    // path limiter (rship_limit_fit): shares the stabiliser's; its own are the goals and the strengths of a call, and what
+    // the kernel keeps between the candidates of a frame (the border's rays)
+    DevBuf limit_goal, limit_out, limit_rays;
     double rect_key_c[10] = {};
     bool rect_rays_c_ok = false;
     int64_t g_first_us = 0, g_last_us = 0;
@@ -1143,7 +1151,8 @@ void rship_destroy(rship_ctx* c) {
                       &c->g_ts, &c->g_rates, &c->g_us, &c->g_dq, &c->g_q, &c->g_knots, &c->g_cf, &c->g_status,
                       &c->trk_slot[0], &c->trk_slot[1], &c->trk_out, &c->ftr_cells, &c->ftr_out,
                       &c->rect_rays, &c->rect_slot[0], &c->rect_slot[1], &c->rect_times, &c->rect_count, &c->rect_tmp,
-                      &c->stab_weights, &c->stab_targets, &c->stab_zooms, &c->stab_cover, &c->rect_rays_c};
+                      &c->stab_weights, &c->stab_targets, &c->stab_zooms, &c->stab_cover, &c->rect_rays_c,
+                      &c->limit_goal, &c->limit_out, &c->limit_rays};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     if (c->pinned) (void)hipHostFree(c->pinned);
@@ -4314,6 +4323,79 @@ int rship_zoom_frames(rship_ctx* c, const uint8_t* frames, uint32_t n_frames, si
                                else if (cfg->filter == 0) hipLaunchKernelGGL((zoom_render_kernel<1, 0>), grid, dim3(256), 0, c->stream, Z);
                                else hipLaunchKernelGGL((zoom_render_kernel<1, 1>), grid, dim3(256), 0, c->stream, Z);
                            });
+}
+
+} // extern "C"
+
+// ===========================================================================
+// path limiter (kernels/limit.hpp; declared in limit_hip.h, called by limit_api.cpp).  rship_zoom_fit's pipeline: the same
+// chunks, one stream, one wait; the kernel builds the row tables itself, so no rows kernel runs in front of it.
+
+extern "C" {
+
+int rship_limit_fit(rship_ctx* c, const double* frame_times, uint32_t n_frames, const double* targets, const rship_stabilize_cfg* cfg,
+                    const double* zooms, int32_t steps, double* strengths, uint32_t* status) {
+    DeviceGuard dev_guard(c);
+    if (stab_check(c, cfg)) return 1;
+    if (steps < 1 || steps > rs::kLimitMaxSteps) return set_err(c, "limit: bad steps");
+    if (!n_frames) return 0;
+    if (!frame_times || !zooms || !strengths) return set_err(c, "limit: null pointer");
+    for (uint32_t f = 0; f < n_frames; ++f)
+        if (!(zooms[f] > 0.0) || !std::isfinite(zooms[f])) return set_err(c, "limit: every zoom must be finite and > 0");
+    const uint32_t h = cfg->height, ow = cfg->out_width, oh = cfg->out_height, n_border = 2 * (ow + oh) - 4;
+    const size_t tab = (size_t)(h + 1) * 9 * sizeof(float);
+    const uint32_t chunk = (uint32_t)std::min<uint64_t>(std::min(n_frames, 65535u), std::max<uint64_t>(1, kStabCoverTables / tab));
+    const bool lens_cam = cfg->camera == 0; // (its border rays are kept between the candidates of a frame)
+    // (the sweep's buffers: its zooms hold the frames' zooms, its counts the statuses)
+    if (ensure(c, c->rect_slot[0], (size_t)chunk * tab) || ensure(c, c->rect_times, (size_t)n_frames * 8) ||
+        ensure(c, c->stab_zooms, (size_t)n_frames * 8) || ensure(c, c->stab_cover, (size_t)n_frames * sizeof(uint32_t)) ||
+        ensure(c, c->limit_goal, (size_t)n_frames * 32) || ensure(c, c->limit_out, (size_t)n_frames * 8) ||
+        (lens_cam && ensure(c, c->limit_rays, (size_t)chunk * n_border * sizeof(float4))))
+        return 1;
+    RS_HIP(hipMemcpy(c->rect_times.p, frame_times, (size_t)n_frames * 8, hipMemcpyHostToDevice));
+    RS_HIP(hipMemcpy(c->stab_zooms.p, zooms, (size_t)n_frames * 8, hipMemcpyHostToDevice));
+    // the goals first (an upload that has ended when it returns, or the path kernel on the stream), moved aside on the
+    // stream; then the frames' own orientations, the path at sigma 0, where the stabiliser keeps its targets
+    if (stab_fill_targets(c, cfg, targets, n_frames)) return 1;
+    RS_HIP(hipMemcpyAsync(c->limit_goal.p, c->stab_targets.p, (size_t)n_frames * 32, hipMemcpyDeviceToDevice, c->stream));
+    rship_stabilize_cfg own = *cfg;
+    own.sigma = 0.0;
+    if (stab_fill_targets(c, &own, nullptr, n_frames)) return 1;
+    LimitFitArgs L{};
+    L.table = (const double*)c->coef64.p;
+    L.rows_tab = (float*)c->rect_slot[0].p;
+    L.rays = lens_cam ? (float4*)c->limit_rays.p : nullptr;
+    L.cam = rs::Lens{0.0, cfg->cam[0], cfg->cam[1], cfg->cam[2], cfg->cam[3], cfg->lens[5], cfg->lens[6], cfg->lens[7], cfg->lens[8]};
+    L.lens = stab_lens_f(cfg);
+    L.start = cfg->start;
+    L.fs = cfg->fs;
+    L.ro = cfg->lens[0];
+    L.delay = cfg->delay;
+    L.y_scale = (float)cfg->height / (float)cfg->out_height;
+    L.n_knots = c->n_knots;
+    L.width = cfg->width;
+    L.height = h;
+    L.out_width = ow;
+    L.out_height = oh;
+    L.n_border = n_border;
+    L.iterations = cfg->iterations;
+    L.camera = cfg->camera;
+    L.steps = steps;
+    // every chunk on the one stream (a chunk's slots are done with before the next chunk's kernel writes them), one wait
+    for (uint32_t f0 = 0; f0 < n_frames; f0 += chunk) {
+        const uint32_t cnt = std::min(chunk, n_frames - f0);
+        L.times = (const double*)c->rect_times.p + f0;
+        L.own = (const double*)c->stab_targets.p + (size_t)f0 * 4;
+        L.goal = (const double*)c->limit_goal.p + (size_t)f0 * 4;
+        L.cams = (const double*)c->stab_zooms.p + f0;
+        L.strengths = (double*)c->limit_out.p + f0;
+        L.status = (uint32_t*)c->stab_cover.p + f0;
+        hipLaunchKernelGGL(limit_fit_kernel, dim3(cnt), dim3(256), 0, c->stream, L);
+        RS_HIP(hipGetLastError());
+    }
+    RS_HIP(hipMemcpyAsync(strengths, c->limit_out.p, (size_t)n_frames * 8, hipMemcpyDeviceToHost, c->stream));
+    if (status) RS_HIP(hipMemcpyAsync(status, c->stab_cover.p, (size_t)n_frames * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    return sync_stream(c);
 }
 
 } // extern "C"

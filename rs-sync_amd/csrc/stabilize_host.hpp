@@ -6,6 +6,7 @@
 #include "../../include/rssync_c.h"
 #include "../../include/rssync_stabilize.h"
 #include "host_errors.hpp"
+#include "limit_math.hpp"
 #include "stabilize_hip.h"
 
 #include <cmath>
@@ -117,10 +118,9 @@ inline void check_frame_time(const rship_stabilize_cfg& c, double t, size_t k) {
 inline std::vector<double> unit_targets(const double* targets, size_t n) {
     std::vector<double> u(n * 4);
     for (size_t k = 0; k < n; ++k) {
-        const double* q = targets + 4 * k;
-        const double norm = std::sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
+        // (rs::limit_unit: the one normalisation, which the path limiter's kernel applies to its candidates as well)
+        const double norm = rs::limit_unit(targets + 4 * k, u.data() + 4 * k);
         if (!std::isfinite(norm) || !(norm > 0)) panic("stabilize: target " + std::to_string(k) + " is zero or not finite");
-        for (int i = 0; i < 4; ++i) u[4 * k + i] = q[i] / norm;
     }
     return u;
 }

@@ -782,6 +782,29 @@ class SyncProblem:
         from . import colorzoom
         return colorzoom.dynamic_zoom_color(self, fmt, width, height, lens, frame_times, delay, lo, hi, window, **params)
 
+    def fit_strength(self, width, height, lens, frame_times, delay, **params):
+        """-> (strengths (n,), status (n,)): how far every frame may follow its goal at a fixed zoom without showing a
+        border, found by a bisection on the device (include/rssync_limit.h, rssync_amd.limit).  params: zoom, zooms, steps,
+        targets, out_size, sigma, camera, out_camera, iterations."""
+        from . import limit
+        return limit.fit_strength(self, width, height, lens, frame_times, delay, **params)
+
+    def smooth_strengths(self, frame_times, strengths, window):
+        """-> (n,): the lower envelope of a fitted strength curve over `window` seconds, never above the curve."""
+        from . import limit
+        return limit.smooth_strengths(self, frame_times, strengths, window)
+
+    def strength_targets(self, frame_times, ro, delay, strengths, **params):
+        """-> (n, 4): every frame's target at its strength between its own orientation and its goal.  params: targets, sigma."""
+        from . import limit
+        return limit.strength_targets(self, frame_times, ro, delay, strengths, **params)
+
+    def limited_targets(self, width, height, lens, frame_times, delay, window, **params):
+        """-> (targets (n, 4), strengths (n,), status (n,)): fit_strength, smooth_strengths and the targets that result,
+        for any renderer's `targets`.  params: fit_strength's, and verify (one coverage call; raises where not clear)."""
+        from . import limit
+        return limit.limited_targets(self, width, height, lens, frame_times, delay, window, **params)
+
     def device_context(self):
         """rship_ctx* of this problem (include/rssync_hip.h), for kernel-level tools."""
         return self._lib.rssync_ext_device_context(self._h)
