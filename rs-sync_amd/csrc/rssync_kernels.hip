@@ -63,6 +63,7 @@
 #include "zoom_hip.h"
 #include "limit_hip.h"
 #include "colorzoom_hip.h"
+#include "infill_hip.h"
 #include "device_math.hpp"
 #include "sync_math.hpp"
 #include "lens_math.hpp"
@@ -72,6 +73,7 @@
 #include "resample_math.hpp"
 #include "zoom_math.hpp"
 #include "limit_math.hpp"
+#include "infill_math.hpp"
 #include "gyro_math.hpp"
 #include "gyro_signal_math.hpp"
 #include "window_plan.hpp"
@@ -102,6 +104,7 @@ using rs::f4;
 #include "kernels/zoom.hpp"
 #include "kernels/limit.hpp"
 #include "kernels/colorzoom.hpp"
+#include "kernels/infill.hpp"
 
 // ===========================================================================
 // host side of the C-ABI
@@ -4830,6 +4833,135 @@ int rship_colorzoom_frames(rship_ctx* c, const rship_color_image* in, uint32_t n
         case 19: percam_launch2<PercamI010>(c, lens_cam, cubic, grid_c, P); break;
         }
     });
+}
+
+} // extern "C"
+
+// ===========================================================================
+// infill (kernels/infill.hpp; declared in infill_hip.h, called by infill_api.cpp).  The chunk pipeline of stab_frames_run
+// with a halo: a chunk of output frames reads its own input frames and `radius` more on each side.  Host frames: a slot
+// holds the chunk with its halo, uploaded anew for every chunk.  Device frames: the kernel reads the neighbours in place.
+
+extern "C" {
+
+int rship_infill_frames(rship_ctx* c, const uint8_t* frames, uint32_t n_frames, size_t pitch, size_t frame_stride,
+                        const double* frame_times, const double* targets, const rship_stabilize_cfg* cfg, uint8_t* out,
+                        size_t out_pitch, size_t out_stride, uint64_t* n_outside, int32_t radius, uint64_t* n_borrowed,
+                        size_t budget_bytes) {
+    DeviceGuard dev_guard(c);
+    if (stab_check(c, cfg)) return 1;
+    if (radius < 0 || radius > rs::kInfillMaxRadius) return set_err(c, "infill: radius must be 0 .. 8");
+    if (!frames || !out || !frame_times) return set_err(c, "stabilize: null pointer");
+    if (!n_frames) return 0;
+    const uint32_t w = cfg->width, h = cfg->height, ow = cfg->out_width, oh = cfg->out_height, r = (uint32_t)radius, places = 2 * r + 1;
+    if (pitch < w || out_pitch < ow || (n_frames > 1 && (frame_stride < pitch * h || out_stride < out_pitch * oh)))
+        return set_err(c, "stabilize: pitch or frame stride too small");
+    bool dev_in = false, dev_out = false;
+    if (rect_pointer(c, frames, "the frames", &dev_in, "stabilize") || rect_pointer(c, out, "the stabilised frames", &dev_out, "stabilize")) return 1;
+    // the chunk: per output frame its tables, its input and its output; per slot the halo's input frames besides
+    const size_t px_in = (size_t)w * h, px_out = (size_t)ow * oh, tab = (size_t)(h + 1) * 9 * sizeof(float);
+    const size_t per_frame = places * tab + (dev_in ? 0 : px_in) + (dev_out ? 0 : px_out);
+    const size_t halo = dev_in ? 0 : (size_t)std::min<uint64_t>(2 * r, n_frames - 1) * px_in;
+    const size_t budget = (budget_bytes ? budget_bytes : kRectBudget) / 2;
+    const uint32_t chunk = (uint32_t)std::min<uint64_t>(std::min(n_frames, kRectMaxChunk), std::max<uint64_t>(1, (budget > halo ? budget - halo : 0) / per_frame));
+    const uint32_t held = (uint32_t)std::min<uint64_t>(n_frames, (uint64_t)chunk + 2 * r); // input frames of a slot
+    const size_t tab_bytes = ((size_t)chunk * places * tab + 255) / 256 * 256;
+    const size_t slot_bytes = tab_bytes + (dev_in ? 0 : (size_t)held * px_in) + (dev_out ? 0 : (size_t)chunk * px_out);
+    for (uint32_t s = 0; s < (n_frames > chunk ? 2u : 1u); ++s)
+        if (ensure(c, c->rect_slot[s], slot_bytes)) return 1;
+    // (the counts: [0, n_frames) the filled pixels, [n_frames, 2 n_frames) the borrowed ones)
+    if (ensure(c, c->rect_times, (size_t)n_frames * 8) || ensure(c, c->rect_count, (size_t)n_frames * 16) || rect_events(c)) return 1;
+    RS_HIP(hipMemcpy(c->rect_times.p, frame_times, (size_t)n_frames * 8, hipMemcpyHostToDevice));
+    RS_HIP(hipMemsetAsync(c->rect_count.p, 0, (size_t)n_frames * 16, c->stream));
+    if (stab_fill_targets(c, cfg, targets, n_frames) || stab_rays(c, cfg)) return 1;
+    InfillRowsArgs R{};
+    R.table = (const double*)c->coef64.p;
+    R.times = (const double*)c->rect_times.p;
+    R.targets = (const double*)c->stab_targets.p;
+    R.start = cfg->start;
+    R.fs = cfg->fs;
+    R.ro = cfg->lens[0];
+    R.delay = cfg->delay;
+    R.n_knots = c->n_knots;
+    R.rows = h;
+    R.n_frames = n_frames;
+    R.radius = radius;
+    const StabArgs S = stab_args(c, cfg);
+    InfillArgs A{};
+    A.rays = S.rays;
+    A.lens = S.lens;
+    A.cam = S.cam;
+    A.y_scale = S.y_scale;
+    A.width = w;
+    A.height = h;
+    A.out_width = ow;
+    A.out_height = oh;
+    A.iterations = S.iterations;
+    A.fill = S.fill;
+    A.n_frames = n_frames;
+    A.radius = radius;
+    // the first and one past the last input frame of the chunk f0 .. f0 + cnt - 1
+    auto first_in = [&](uint32_t f0) { return f0 > r ? f0 - r : 0u; };
+    auto end_in = [&](uint32_t f0, uint32_t cnt) { return (uint32_t)std::min<uint64_t>(n_frames, (uint64_t)f0 + cnt + r); };
+    auto upload = [&](int slot, bool reused, uint32_t f0, uint32_t cnt) -> int {
+        if (reused) RS_HIP(hipStreamWaitEvent(c->copy_stream, c->trk_k[slot], 0));
+        const uint32_t lo = first_in(f0);
+        if (!dev_in && rect_copy(c, (uint8_t*)c->rect_slot[slot].p + tab_bytes, w, px_in, frames + (size_t)lo * frame_stride, pitch, frame_stride, w, h,
+                                 end_in(f0, cnt) - lo))
+            return 1;
+        RS_HIP(hipEventRecord(c->trk_up[slot], c->copy_stream));
+        return 0;
+    };
+    const dim3 grid((ow + kRectTW - 1) / kRectTW, (oh + kRectTH - 1) / kRectTH, 1);
+    bool used[2] = {false, false};
+    int slot = 0;
+    if (upload(0, false, 0, std::min(chunk, n_frames))) return 1;
+    for (uint32_t f0 = 0; f0 < n_frames;) {
+        const uint32_t cnt = std::min(chunk, n_frames - f0);
+        uint8_t* base = (uint8_t*)c->rect_slot[slot].p;
+        uint8_t* s_in = base + tab_bytes;
+        uint8_t* s_out = s_in + (dev_in ? 0 : (size_t)held * px_in);
+        RS_HIP(hipStreamWaitEvent(c->stream, c->trk_up[slot], 0));
+        R.rows_tab = (float*)base;
+        R.f0 = f0;
+        hipLaunchKernelGGL(infill_rows_kernel, dim3((h + 1 + 255) / 256, places, cnt), dim3(256), 0, c->stream, R);
+        RS_HIP(hipGetLastError());
+        A.rows_tab = (const float*)base;
+        A.outside = (unsigned long long*)c->rect_count.p + f0;
+        A.borrowed = (unsigned long long*)c->rect_count.p + n_frames + f0;
+        A.f0 = f0;
+        if (dev_in) { A.src = frames; A.src0 = 0; A.src_pitch = pitch; A.src_stride = frame_stride; }
+        else { A.src = s_in; A.src0 = first_in(f0); A.src_pitch = w; A.src_stride = px_in; }
+        if (dev_out) { A.dst = out + (size_t)f0 * out_stride; A.dst_pitch = out_pitch; A.dst_stride = out_stride; }
+        else { A.dst = s_out; A.dst_pitch = ow; A.dst_stride = px_out; }
+        const dim3 g(grid.x, grid.y, cnt);
+        if (cfg->camera == 0 && cfg->filter == 0) hipLaunchKernelGGL((infill_kernel<0, 0>), g, dim3(256), 0, c->stream, A);
+        else if (cfg->camera == 0) hipLaunchKernelGGL((infill_kernel<0, 1>), g, dim3(256), 0, c->stream, A);
+        else if (cfg->filter == 0) hipLaunchKernelGGL((infill_kernel<1, 0>), g, dim3(256), 0, c->stream, A);
+        else hipLaunchKernelGGL((infill_kernel<1, 1>), g, dim3(256), 0, c->stream, A);
+        RS_HIP(hipGetLastError());
+        RS_HIP(hipEventRecord(c->trk_k[slot], c->stream));
+        used[slot] = true;
+        const uint32_t next = f0 + cnt;
+        if (next < n_frames && upload(slot ^ 1, used[slot ^ 1], next, std::min(chunk, n_frames - next))) return 1;
+        if (!dev_out) {
+            RS_HIP(hipStreamWaitEvent(c->copy_stream, c->trk_k[slot], 0));
+            if (rect_copy(c, out + (size_t)f0 * out_stride, out_pitch, out_stride, s_out, ow, px_out, ow, oh, cnt)) return 1;
+        }
+        f0 = next;
+        slot ^= 1;
+    }
+    // both counts in one download
+    std::vector<uint64_t> counts;
+    if (n_outside || n_borrowed) {
+        counts.resize((size_t)n_frames * 2);
+        RS_HIP(hipMemcpyAsync(counts.data(), c->rect_count.p, (size_t)n_frames * 16, hipMemcpyDeviceToHost, c->stream));
+    }
+    RS_HIP(hipStreamSynchronize(c->copy_stream));
+    if (sync_stream(c)) return 1;
+    if (n_outside) std::copy(counts.begin(), counts.begin() + n_frames, n_outside);
+    if (n_borrowed) std::copy(counts.begin() + n_frames, counts.end(), n_borrowed);
+    return 0;
 }
 
 } // extern "C"

@@ -743,6 +743,18 @@ class SyncProblem:
         from . import zoom
         return zoom.stabilize_frames_zoomed_budget(self, frames, frame_times, lens, delay, zooms, budget_bytes, **params)
 
+    def stabilize_frames_infilled(self, frames, frame_times, lens, delay, radius, **params):
+        """stabilize_frames with the borders taken from up to `radius` neighbouring frames of the call on each side
+        (include/rssync_infill.h, rssync_amd.infill) -> (frames (n, out_height, out_width), n_outside (n,), n_borrowed (n,)).
+        params: targets, out_size, out, sigma, zoom, camera, out_camera, iterations, fill, filter."""
+        from . import infill
+        return infill.stabilize_frames_infilled(self, frames, frame_times, lens, delay, radius, **params)
+
+    def stabilize_frames_infilled_budget(self, frames, frame_times, lens, delay, radius, budget_bytes, **params):
+        """stabilize_frames_infilled through the internal launcher with a device budget for its chunk slots (tests)."""
+        from . import infill
+        return infill.stabilize_frames_infilled_budget(self, frames, frame_times, lens, delay, radius, budget_bytes, **params)
+
     def stabilize_color(self, fmt, frames, frame_times, lens, delay, **params):
         """Colour frames (rssync_amd.color: GRAY8, NV12, I420, RGBA32, and with uint16 samples GRAY16, P010, P016, I010)
         rendered at the smoothed path's orientations, or at `targets`, all planes of a frame in one pass
