@@ -77,6 +77,7 @@
 #include "gyro_math.hpp"
 #include "gyro_signal_math.hpp"
 #include "window_plan.hpp"
+#include "frame_plan.hpp"
 #include "roctx_ranges.hpp"
 
 using rs::f3;
@@ -3448,6 +3449,44 @@ int track_prepare(rship_ctx* c, const uint8_t* frames, uint32_t n_frames, const 
     return 0;
 }
 
+TrackArgs track_args(const TrackGeom& t, const rship_track_cfg* cfg) {
+    TrackArgs A{};
+    A.pyr_stride = t.pyr_stride;
+    A.u8_stride = t.u8_stride;
+    A.levels = cfg->levels;
+    A.win = cfg->window;
+    A.max_iters = cfg->max_iters;
+    A.eps2 = cfg->epsilon * cfg->epsilon;
+    A.min_eig = cfg->min_eig;
+    A.L = t.L;
+    return A;
+}
+
+// The trackers' chunk loop: chunk j holds frames [f0, f0 + cnt) and its pairs f0 .. f0 + cnt - 2; the next chunk starts at
+// its last frame, so every pair lies in exactly one chunk and a pair's result does not depend on where the chunks are
+// cut.  per_chunk(slot, f0, cnt) enqueues the chunk's kernels on the context's stream after its pyramid.
+template <class F>
+int track_chunks(rship_ctx* c, const TrackGeom& t, const rship_track_cfg* cfg, const uint8_t* frames, uint32_t n_frames, size_t pitch,
+                 size_t fstride, F&& per_chunk) {
+    bool used[2] = {false, false};
+    uint32_t f0 = 0;
+    int slot = 0;
+    if (track_upload(c, t, 0, false, frames, 0, std::min(t.chunk, n_frames), pitch, fstride)) return 1;
+    for (;;) {
+        const uint32_t cnt = std::min(t.chunk, n_frames - f0);
+        if (track_pyramid(c, t, slot, cnt, cfg->levels)) return 1;
+        if (per_chunk(slot, f0, cnt)) return 1;
+        RS_HIP(hipEventRecord(c->trk_k[slot], c->stream));
+        used[slot] = true;
+        const uint32_t next = f0 + cnt - 1;
+        if (next >= n_frames - 1) break;
+        slot ^= 1;
+        if (track_upload(c, t, slot, used[slot], frames, next, std::min(t.chunk, n_frames - next), pitch, fstride)) return 1;
+        f0 = next;
+    }
+    return 0;
+}
+
 } // namespace
 
 extern "C" {
@@ -3466,27 +3505,11 @@ int rship_track_frames(rship_ctx* c, const uint8_t* frames, uint32_t n_frames, s
     float2* d_flow = (float2*)c->trk_out.p;
     float* d_res = (float*)(d_flow + n_out);
     uint8_t* d_st = (uint8_t*)(d_res + n_out);
-    TrackArgs A{};
-    A.pyr_stride = t.pyr_stride;
-    A.u8_stride = t.u8_stride;
-    A.levels = cfg->levels;
+    TrackArgs A = track_args(t, cfg);
     A.n_points = P;
     A.ny = t.ny;
     A.step = cfg->step;
-    A.win = cfg->window;
-    A.max_iters = cfg->max_iters;
-    A.eps2 = cfg->epsilon * cfg->epsilon;
-    A.min_eig = cfg->min_eig;
-    A.L = t.L;
-    // chunk j holds frames [f0, f0 + cnt) and tracks pairs f0 .. f0 + cnt - 2; the next chunk starts at its last frame, so
-    // every pair lies in exactly one chunk and a pair's result does not depend on where the chunks are cut
-    bool used[2] = {false, false};
-    uint32_t f0 = 0;
-    int slot = 0;
-    if (track_upload(c, t, 0, false, frames, 0, std::min(t.chunk, n_frames), pitch, frame_stride)) return 1;
-    for (;;) {
-        const uint32_t cnt = std::min(t.chunk, n_frames - f0);
-        if (track_pyramid(c, t, slot, cnt, cfg->levels)) return 1;
+    auto chunk = [&](int slot, uint32_t f0, uint32_t cnt) -> int {
         A.u8 = (const uint8_t*)c->trk_slot[slot].p;
         A.pyr = (const float*)(A.u8 + (size_t)t.chunk * t.u8_stride);
         A.n_pairs = cnt - 1;
@@ -3496,14 +3519,9 @@ int rship_track_frames(rship_ctx* c, const uint8_t* frames, uint32_t n_frames, s
         const uint32_t waves = A.n_pairs * P;
         hipLaunchKernelGGL(lk_kernel, dim3((waves + 3) / 4), dim3(256), 0, c->stream, A);
         RS_HIP(hipGetLastError());
-        RS_HIP(hipEventRecord(c->trk_k[slot], c->stream));
-        used[slot] = true;
-        const uint32_t next = f0 + cnt - 1;
-        if (next >= n_frames - 1) break;
-        slot ^= 1;
-        if (track_upload(c, t, slot, used[slot], frames, next, std::min(t.chunk, n_frames - next), pitch, frame_stride)) return 1;
-        f0 = next;
-    }
+        return 0;
+    };
+    if (track_chunks(c, t, cfg, frames, n_frames, pitch, frame_stride, chunk)) return 1;
     RS_HIP(hipMemcpyAsync(flow, d_flow, n_out * 8, hipMemcpyDeviceToHost, c->stream));
     RS_HIP(hipMemcpyAsync(residual, d_res, n_out * 4, hipMemcpyDeviceToHost, c->stream));
     RS_HIP(hipMemcpyAsync(status, d_st, n_out, hipMemcpyDeviceToHost, c->stream));
@@ -3529,49 +3547,8 @@ int rship_track_pyramid(rship_ctx* c, const uint8_t* frames, uint32_t n_frames, 
 } // extern "C"
 
 // ===========================================================================
-// corner features and tracking from a list (kernels/features.hpp; declared in track_hip.h, called by features_api.cpp)
-
-namespace {
-
-TrackArgs track_args(const TrackGeom& t, const rship_track_cfg* cfg) {
-    TrackArgs A{};
-    A.pyr_stride = t.pyr_stride;
-    A.u8_stride = t.u8_stride;
-    A.levels = cfg->levels;
-    A.win = cfg->window;
-    A.max_iters = cfg->max_iters;
-    A.eps2 = cfg->epsilon * cfg->epsilon;
-    A.min_eig = cfg->min_eig;
-    A.L = t.L;
-    return A;
-}
-
-// rship_track_frames' chunk loop: chunk j holds frames [f0, f0 + cnt) and its pairs f0 .. f0 + cnt - 2; the next chunk
-// starts at its last frame, so every pair lies in exactly one chunk.  per_chunk(slot, f0, cnt) enqueues the chunk's
-// kernels on the context's stream after its pyramid.
-template <class F>
-int track_chunks(rship_ctx* c, const TrackGeom& t, const rship_track_cfg* cfg, const uint8_t* frames, uint32_t n_frames, size_t pitch,
-                 size_t fstride, F&& per_chunk) {
-    bool used[2] = {false, false};
-    uint32_t f0 = 0;
-    int slot = 0;
-    if (track_upload(c, t, 0, false, frames, 0, std::min(t.chunk, n_frames), pitch, fstride)) return 1;
-    for (;;) {
-        const uint32_t cnt = std::min(t.chunk, n_frames - f0);
-        if (track_pyramid(c, t, slot, cnt, cfg->levels)) return 1;
-        if (per_chunk(slot, f0, cnt)) return 1;
-        RS_HIP(hipEventRecord(c->trk_k[slot], c->stream));
-        used[slot] = true;
-        const uint32_t next = f0 + cnt - 1;
-        if (next >= n_frames - 1) break;
-        slot ^= 1;
-        if (track_upload(c, t, slot, used[slot], frames, next, std::min(t.chunk, n_frames - next), pitch, fstride)) return 1;
-        f0 = next;
-    }
-    return 0;
-}
-
-} // namespace
+// corner features and tracking from a list (kernels/features.hpp; declared in track_hip.h, called by features_api.cpp).
+// The tracker's chunk loop (track_chunks) with kernels of their own.
 
 extern "C" {
 
@@ -3698,12 +3675,6 @@ int rship_track_list(rship_ctx* c, const uint8_t* frames, uint32_t n_frames, siz
 
 namespace {
 
-// Device bytes the rectifier may hold for host frames on their way in and out and for the row tables: two chunk slots
-// (the one the kernels work in, the one the next upload fills) share it.  Not a knob of the product: a chunk is as many
-// frames as fit, at least one (rship_rectify_frames' budget_bytes exists for the tests).
-constexpr size_t kRectBudget = 256ull << 20;
-constexpr uint32_t kRectMaxChunk = 32768; // frames of a chunk are the grid's z
-
 // host memory, or memory of the context's device (*on_device); another device's pointer is an error, not a copy
 int rect_pointer(rship_ctx* c, const void* p, const char* what, bool* on_device, const char* who = "rectify") {
     hipPointerAttribute_t at{};
@@ -3776,12 +3747,6 @@ RectArgs rect_args(rship_ctx* c, const rship_rectify_cfg* g) {
     return A;
 }
 
-int rect_events(rship_ctx* c) {
-    for (hipEvent_t* e : {&c->trk_up[0], &c->trk_up[1], &c->trk_k[0], &c->trk_k[1]}) // (the tracker's: calls do not overlap)
-        if (!*e) RS_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
-    return 0;
-}
-
 // rows [0, h * cnt) of cnt frames between a pitched user buffer and a packed slot, as one copy where the frames' rows are
 // equally spaced
 int rect_copy(rship_ctx* c, uint8_t* dst, size_t dpitch, size_t dstride, const uint8_t* src, size_t spitch, size_t sstride, uint32_t w,
@@ -3792,6 +3757,100 @@ int rect_copy(rship_ctx* c, uint8_t* dst, size_t dpitch, size_t dstride, const u
         for (uint32_t i = 0; i < cnt; ++i)
             RS_HIP(hipMemcpy2DAsync(dst + (size_t)i * dstride, dpitch, src + (size_t)i * sstride, spitch, w, h, hipMemcpyDefault, c->copy_stream));
     return 0;
+}
+
+// ---- the frame pipeline: every frame front door's chunks (the layout: frame_plan.hpp) ----------------------------------
+
+// the plan of a call with one 8-bit plane per frame, w x h in and ow x oh out, and `tabs` row tables per output frame
+rs::FramePlan gray_plan(uint32_t n_frames, size_t budget_bytes, uint32_t tabs, uint32_t radius, uint32_t w, uint32_t h, bool dev_in,
+                        uint32_t ow, uint32_t oh, bool dev_out) {
+    rs::FrameLayout q;
+    q.n_frames = n_frames;
+    q.budget = budget_bytes;
+    q.tab[0] = (size_t)(h + 1) * 9 * sizeof(float);
+    q.tabs = tabs;
+    q.radius = radius;
+    q.n_in = dev_in ? 0 : 1;
+    q.in[0] = {w, h};
+    q.n_out = dev_out ? 0 : 1;
+    q.out[0] = {ow, oh};
+    return rs::plan_frames(q);
+}
+
+rship_color_image gray_image(const uint8_t* p, size_t pitch, size_t stride) { return rship_color_image{{(uint8_t*)p}, {pitch}, {stride}}; }
+
+// What per_chunk gets: frames [f0, f0 + cnt) of the call, their slot (its table regions at the plan's off_tab), and where
+// their planes lie: packed in the slot, or -- device memory -- in the caller's planes.  src points at frame src0 of the
+// call: f0, or the first frame of the chunk's halo that the slot holds.
+struct FrameChunk {
+    uint8_t* base;
+    uint32_t f0, cnt, src0;
+    const uint8_t* src[3];
+    uint8_t* dst[3];
+    uint64_t src_pitch[3], src_stride[3], dst_pitch[3], dst_stride[3];
+};
+
+// The chunk pipeline of every frame front door.  Chunk j = frames [f0, f0 + cnt) in slot j & 1.  The copy stream carries
+// upload(0), upload(1), download(0), upload(2), download(1), ...: an upload into a slot follows the download of the chunk
+// that used it before, and waits for that chunk's kernels; the kernels of a chunk wait for the event recorded after its
+// upload.  per_chunk(K) enqueues the chunk's rows kernel and render kernel on the context's stream.  `in` and `out` are the
+// caller's np planes; a side with no planes in the plan is device memory and is read or written in place.  At the end
+// n_counts words of c->rect_count go to `counts` (host; NULL: none) and both streams are waited for.
+template <class PerChunk>
+int frame_pipeline(rship_ctx* c, const rs::FramePlan& P, int np, const rship_color_image& in, const rship_color_image& out, uint64_t* counts,
+                   size_t n_counts, PerChunk&& per_chunk) {
+    const uint32_t n_frames = P.n_frames, chunk = P.chunk, r = P.radius;
+    for (uint32_t s = 0; s < (P.two_slots ? 2u : 1u); ++s)
+        if (ensure(c, c->rect_slot[s], P.slot_bytes)) return 1;
+    for (hipEvent_t* e : {&c->trk_up[0], &c->trk_up[1], &c->trk_k[0], &c->trk_k[1]}) // (the tracker's: calls do not overlap)
+        if (!*e) RS_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
+    // a chunk's input frames [lo_in(f0), end_in(f0, cnt)): its own and the halo's
+    auto lo_in = [&](uint32_t f0) { return f0 > r ? f0 - r : 0u; };
+    auto end_in = [&](uint32_t f0, uint32_t cnt) { return (uint32_t)std::min<uint64_t>(n_frames, (uint64_t)f0 + cnt + r); };
+    auto upload = [&](int slot, bool reused, uint32_t f0, uint32_t cnt) -> int {
+        if (reused) RS_HIP(hipStreamWaitEvent(c->copy_stream, c->trk_k[slot], 0));
+        const uint32_t lo = lo_in(f0);
+        for (int k = 0; k < P.n_in; ++k)
+            if (rect_copy(c, (uint8_t*)c->rect_slot[slot].p + P.off_in[k], P.in[k].row_bytes, P.in[k].bytes(), in.plane[k] + (size_t)lo * in.stride[k],
+                          in.pitch[k], in.stride[k], (uint32_t)P.in[k].row_bytes, P.in[k].rows, end_in(f0, cnt) - lo))
+                return 1;
+        RS_HIP(hipEventRecord(c->trk_up[slot], c->copy_stream));
+        return 0;
+    };
+    bool used[2] = {false, false};
+    int slot = 0;
+    if (upload(0, false, 0, std::min(chunk, n_frames))) return 1;
+    for (uint32_t f0 = 0; f0 < n_frames;) {
+        FrameChunk K{};
+        K.base = (uint8_t*)c->rect_slot[slot].p;
+        K.f0 = f0;
+        K.cnt = std::min(chunk, n_frames - f0);
+        K.src0 = P.n_in ? lo_in(f0) : f0;
+        for (int k = 0; k < np; ++k) {
+            if (!P.n_in) { K.src[k] = in.plane[k] + (size_t)f0 * in.stride[k]; K.src_pitch[k] = in.pitch[k]; K.src_stride[k] = in.stride[k]; }
+            else { K.src[k] = K.base + P.off_in[k]; K.src_pitch[k] = P.in[k].row_bytes; K.src_stride[k] = P.in[k].bytes(); }
+            if (!P.n_out) { K.dst[k] = out.plane[k] + (size_t)f0 * out.stride[k]; K.dst_pitch[k] = out.pitch[k]; K.dst_stride[k] = out.stride[k]; }
+            else { K.dst[k] = K.base + P.off_out[k]; K.dst_pitch[k] = P.out[k].row_bytes; K.dst_stride[k] = P.out[k].bytes(); }
+        }
+        RS_HIP(hipStreamWaitEvent(c->stream, c->trk_up[slot], 0));
+        if (per_chunk(K)) return 1;
+        RS_HIP(hipEventRecord(c->trk_k[slot], c->stream));
+        used[slot] = true;
+        const uint32_t next = f0 + K.cnt;
+        if (next < n_frames && upload(slot ^ 1, used[slot ^ 1], next, std::min(chunk, n_frames - next))) return 1;
+        if (P.n_out) {
+            RS_HIP(hipStreamWaitEvent(c->copy_stream, c->trk_k[slot], 0));
+            for (int k = 0; k < P.n_out; ++k)
+                if (rect_copy(c, out.plane[k] + (size_t)f0 * out.stride[k], out.pitch[k], out.stride[k], K.dst[k], P.out[k].row_bytes, P.out[k].bytes(),
+                              (uint32_t)P.out[k].row_bytes, P.out[k].rows, K.cnt))
+                    return 1;
+        }
+        f0 = next;
+        slot ^= 1;
+    }
+    if (counts) RS_HIP(hipMemcpyAsync(counts, c->rect_count.p, n_counts * 8, hipMemcpyDeviceToHost, c->stream));
+    RS_HIP(hipStreamSynchronize(c->copy_stream));
+    return sync_stream(c);
 }
 
 } // namespace
@@ -3810,66 +3869,28 @@ int rship_rectify_frames(rship_ctx* c, const uint8_t* frames, uint32_t n_frames,
         return set_err(c, "rectify: pitch or frame stride too small");
     bool dev_in = false, dev_out = false;
     if (rect_pointer(c, frames, "the frames", &dev_in) || rect_pointer(c, out, "the rectified frames", &dev_out)) return 1;
-    const size_t px = (size_t)w * h, tab = (size_t)(h + 1) * 9 * sizeof(float);
-    const size_t per_frame = tab + (dev_in ? 0 : px) + (dev_out ? 0 : px);
-    const size_t budget = budget_bytes ? budget_bytes : kRectBudget;
-    const uint32_t chunk = (uint32_t)std::min<uint64_t>(std::min(n_frames, kRectMaxChunk), std::max<uint64_t>(1, budget / 2 / per_frame));
-    const size_t tab_bytes = ((size_t)chunk * tab + 255) / 256 * 256;
-    const size_t slot_bytes = tab_bytes + (size_t)chunk * (per_frame - tab);
-    for (uint32_t s = 0; s < (n_frames > chunk ? 2u : 1u); ++s)
-        if (ensure(c, c->rect_slot[s], slot_bytes)) return 1;
-    if (ensure(c, c->rect_times, (size_t)n_frames * 8) || ensure(c, c->rect_count, (size_t)n_frames * 8) || rect_events(c)) return 1;
+    const rs::FramePlan P = gray_plan(n_frames, budget_bytes, 1, 0, w, h, dev_in, w, h, dev_out);
+    if (ensure(c, c->rect_times, (size_t)n_frames * 8) || ensure(c, c->rect_count, (size_t)n_frames * 8)) return 1;
     RS_HIP(hipMemcpy(c->rect_times.p, frame_times, (size_t)n_frames * 8, hipMemcpyHostToDevice));
     RS_HIP(hipMemsetAsync(c->rect_count.p, 0, (size_t)n_frames * 8, c->stream));
     if (rect_rays(c, cfg)) return 1;
     RectRowsArgs R = rect_rows_args(c, cfg);
     RectArgs A = rect_args(c, cfg);
-    // chunk j = frames [f0, f0 + cnt) in slot j & 1.  The copy stream carries upload(0), upload(1), download(0), upload(2),
-    // download(1), ...: an upload into a slot follows the download of the chunk that used it before, and waits for that
-    // chunk's kernels; the kernels of a chunk wait for the event recorded after its upload.
-    auto upload = [&](int slot, bool reused, uint32_t f0, uint32_t cnt) -> int {
-        if (reused) RS_HIP(hipStreamWaitEvent(c->copy_stream, c->trk_k[slot], 0));
-        if (!dev_in && rect_copy(c, (uint8_t*)c->rect_slot[slot].p + tab_bytes, w, px, frames + (size_t)f0 * frame_stride, pitch, frame_stride, w, h, cnt))
-            return 1;
-        RS_HIP(hipEventRecord(c->trk_up[slot], c->copy_stream));
+    return frame_pipeline(c, P, 1, gray_image(frames, pitch, frame_stride), gray_image(out, out_pitch, out_stride), n_outside, n_frames,
+                          [&](const FrameChunk& K) -> int {
+        R.times = (const double*)c->rect_times.p + K.f0;
+        R.rows_tab = (float*)K.base;
+        R.n_frames = K.cnt;
+        hipLaunchKernelGGL(rectify_rows_kernel, dim3((h + 1 + 255) / 256, K.cnt), dim3(256), 0, c->stream, R);
+        RS_HIP(hipGetLastError());
+        A.rows_tab = (const float*)K.base;
+        A.outside = (unsigned long long*)c->rect_count.p + K.f0;
+        A.src = K.src[0]; A.src_pitch = K.src_pitch[0]; A.src_stride = K.src_stride[0];
+        A.dst = K.dst[0]; A.dst_pitch = K.dst_pitch[0]; A.dst_stride = K.dst_stride[0];
+        hipLaunchKernelGGL(rectify_kernel<false>, dim3((w + kRectTW - 1) / kRectTW, (h + kRectTH - 1) / kRectTH, K.cnt), dim3(256), 0, c->stream, A);
+        RS_HIP(hipGetLastError());
         return 0;
-    };
-    bool used[2] = {false, false};
-    int slot = 0;
-    if (upload(0, false, 0, std::min(chunk, n_frames))) return 1;
-    for (uint32_t f0 = 0; f0 < n_frames;) {
-        const uint32_t cnt = std::min(chunk, n_frames - f0);
-        uint8_t* base = (uint8_t*)c->rect_slot[slot].p;
-        uint8_t* s_in = base + tab_bytes;
-        uint8_t* s_out = s_in + (dev_in ? 0 : (size_t)chunk * px);
-        RS_HIP(hipStreamWaitEvent(c->stream, c->trk_up[slot], 0));
-        R.times = (const double*)c->rect_times.p + f0;
-        R.rows_tab = (float*)base;
-        R.n_frames = cnt;
-        hipLaunchKernelGGL(rectify_rows_kernel, dim3((h + 1 + 255) / 256, cnt), dim3(256), 0, c->stream, R);
-        RS_HIP(hipGetLastError());
-        A.rows_tab = (const float*)base;
-        A.outside = (unsigned long long*)c->rect_count.p + f0;
-        if (dev_in) { A.src = frames + (size_t)f0 * frame_stride; A.src_pitch = pitch; A.src_stride = frame_stride; }
-        else { A.src = s_in; A.src_pitch = w; A.src_stride = px; }
-        if (dev_out) { A.dst = out + (size_t)f0 * out_stride; A.dst_pitch = out_pitch; A.dst_stride = out_stride; }
-        else { A.dst = s_out; A.dst_pitch = w; A.dst_stride = px; }
-        hipLaunchKernelGGL(rectify_kernel<false>, dim3((w + kRectTW - 1) / kRectTW, (h + kRectTH - 1) / kRectTH, cnt), dim3(256), 0, c->stream, A);
-        RS_HIP(hipGetLastError());
-        RS_HIP(hipEventRecord(c->trk_k[slot], c->stream));
-        used[slot] = true;
-        const uint32_t next = f0 + cnt;
-        if (next < n_frames && upload(slot ^ 1, used[slot ^ 1], next, std::min(chunk, n_frames - next))) return 1;
-        if (!dev_out) {
-            RS_HIP(hipStreamWaitEvent(c->copy_stream, c->trk_k[slot], 0));
-            if (rect_copy(c, out + (size_t)f0 * out_stride, out_pitch, out_stride, s_out, w, px, w, h, cnt)) return 1;
-        }
-        f0 = next;
-        slot ^= 1;
-    }
-    if (n_outside) RS_HIP(hipMemcpyAsync(n_outside, c->rect_count.p, (size_t)n_frames * 8, hipMemcpyDeviceToHost, c->stream));
-    RS_HIP(hipStreamSynchronize(c->copy_stream));
-    return sync_stream(c);
+    });
 }
 
 int rship_rectify_map(rship_ctx* c, double frame_time, const rship_rectify_cfg* cfg, float* map_xy) {
@@ -4035,23 +4056,32 @@ StabArgs stab_args(rship_ctx* c, const rship_stabilize_cfg* g) {
     return A;
 }
 
-template <bool MAP>
-void stab_launch(rship_ctx* c, const rship_stabilize_cfg* g, const StabArgs& A, uint32_t cnt) {
-    const dim3 grid((g->out_width + kRectTW - 1) / kRectTW, (g->out_height + kRectTH - 1) / kRectTH, cnt);
-    if (!MAP && g->filter == 1) { // RSSYNC_FILTER_BICUBIC (kernels/resample.hpp); the map does not depend on the filter
-        if (g->camera == 0)
-            hipLaunchKernelGGL((stabilize_bicubic_kernel<0>), grid, dim3(256), 0, c->stream, A);
-        else
-            hipLaunchKernelGGL((stabilize_bicubic_kernel<1>), grid, dim3(256), 0, c->stream, A);
-        return;
-    }
-    if (g->camera == 0)
-        hipLaunchKernelGGL((stabilize_kernel<0, MAP>), grid, dim3(256), 0, c->stream, A);
-    else
-        hipLaunchKernelGGL((stabilize_kernel<1, MAP>), grid, dim3(256), 0, c->stream, A);
+// the <camera, filter> instantiation of a kernel family: Pick<C, F>::kernel
+template <template <int, int> class Pick, class... Args>
+void camfilt_launch(rship_ctx* c, int camera, int filter, dim3 grid, const Args&... args) {
+    if (camera == 0 && filter == 0) hipLaunchKernelGGL((Pick<0, 0>::kernel), grid, dim3(256), 0, c->stream, args...);
+    else if (camera == 0) hipLaunchKernelGGL((Pick<0, 1>::kernel), grid, dim3(256), 0, c->stream, args...);
+    else if (filter == 0) hipLaunchKernelGGL((Pick<1, 0>::kernel), grid, dim3(256), 0, c->stream, args...);
+    else hipLaunchKernelGGL((Pick<1, 1>::kernel), grid, dim3(256), 0, c->stream, args...);
 }
 
-// The chunk pipeline of the frames: rship_stabilize_frames' and rship_zoom_frames'.  launch(A, f0, cnt) enqueues the
+// filter 1: RSSYNC_FILTER_BICUBIC (kernels/resample.hpp); the map does not depend on the filter
+template <int C, int F> struct PickStab { static constexpr auto kernel = stabilize_kernel<C, false>; };
+template <int C> struct PickStab<C, 1> { static constexpr auto kernel = stabilize_bicubic_kernel<C>; };
+template <int C, int F> struct PickStabMap { static constexpr auto kernel = stabilize_kernel<C, true>; };
+template <int C, int F> struct PickZoom { static constexpr auto kernel = zoom_render_kernel<C, F>; };
+
+dim3 stab_grid(const rship_stabilize_cfg* g, uint32_t cnt) {
+    return dim3((g->out_width + kRectTW - 1) / kRectTW, (g->out_height + kRectTH - 1) / kRectTH, cnt);
+}
+
+template <bool MAP>
+void stab_launch(rship_ctx* c, const rship_stabilize_cfg* g, const StabArgs& A, uint32_t cnt) {
+    if constexpr (MAP) camfilt_launch<PickStabMap>(c, g->camera, g->filter, stab_grid(g, cnt), A);
+    else camfilt_launch<PickStab>(c, g->camera, g->filter, stab_grid(g, cnt), A);
+}
+
+// The frames of rship_stabilize_frames and rship_zoom_frames through frame_pipeline.  launch(A, f0, cnt) enqueues the
 // kernel that renders the chunk's cnt frames, the first of which is frame f0 of the call; ray_map: the cached ray map of
 // cfg's output camera is needed.
 template <class Launch>
@@ -4065,64 +4095,52 @@ int stab_frames_run(rship_ctx* c, const uint8_t* frames, uint32_t n_frames, size
         return set_err(c, "stabilize: pitch or frame stride too small");
     bool dev_in = false, dev_out = false;
     if (rect_pointer(c, frames, "the frames", &dev_in, "stabilize") || rect_pointer(c, out, "the stabilised frames", &dev_out, "stabilize")) return 1;
-    const size_t px_in = (size_t)w * h, px_out = (size_t)ow * oh, tab = (size_t)(h + 1) * 9 * sizeof(float);
-    const size_t per_frame = tab + (dev_in ? 0 : px_in) + (dev_out ? 0 : px_out);
-    const size_t budget = budget_bytes ? budget_bytes : kRectBudget;
-    const uint32_t chunk = (uint32_t)std::min<uint64_t>(std::min(n_frames, kRectMaxChunk), std::max<uint64_t>(1, budget / 2 / per_frame));
-    const size_t tab_bytes = ((size_t)chunk * tab + 255) / 256 * 256;
-    const size_t slot_bytes = tab_bytes + (size_t)chunk * (per_frame - tab);
-    for (uint32_t s = 0; s < (n_frames > chunk ? 2u : 1u); ++s)
-        if (ensure(c, c->rect_slot[s], slot_bytes)) return 1;
-    if (ensure(c, c->rect_times, (size_t)n_frames * 8) || ensure(c, c->rect_count, (size_t)n_frames * 8) || rect_events(c)) return 1;
+    const rs::FramePlan P = gray_plan(n_frames, budget_bytes, 1, 0, w, h, dev_in, ow, oh, dev_out);
+    if (ensure(c, c->rect_times, (size_t)n_frames * 8) || ensure(c, c->rect_count, (size_t)n_frames * 8)) return 1;
     RS_HIP(hipMemcpy(c->rect_times.p, frame_times, (size_t)n_frames * 8, hipMemcpyHostToDevice));
     RS_HIP(hipMemsetAsync(c->rect_count.p, 0, (size_t)n_frames * 8, c->stream));
     if (stab_fill_targets(c, cfg, targets, n_frames) || (ray_map && stab_rays(c, cfg))) return 1;
     StabRowsArgs R = stab_rows_args(c, cfg);
     StabArgs A = stab_args(c, cfg);
-    // the chunk pipeline of rship_rectify_frames: chunk j in slot j & 1, uploads and downloads on the copy stream
-    auto upload = [&](int slot, bool reused, uint32_t f0, uint32_t cnt) -> int {
-        if (reused) RS_HIP(hipStreamWaitEvent(c->copy_stream, c->trk_k[slot], 0));
-        if (!dev_in && rect_copy(c, (uint8_t*)c->rect_slot[slot].p + tab_bytes, w, px_in, frames + (size_t)f0 * frame_stride, pitch, frame_stride, w, h, cnt))
-            return 1;
-        RS_HIP(hipEventRecord(c->trk_up[slot], c->copy_stream));
+    return frame_pipeline(c, P, 1, gray_image(frames, pitch, frame_stride), gray_image(out, out_pitch, out_stride), n_outside, n_frames,
+                          [&](const FrameChunk& K) -> int {
+        R.times = (const double*)c->rect_times.p + K.f0;
+        R.targets = (const double*)c->stab_targets.p + (size_t)K.f0 * 4;
+        R.rows_tab = (float*)K.base;
+        R.n_frames = K.cnt;
+        hipLaunchKernelGGL(stabilize_rows_kernel, dim3((h + 1 + 255) / 256, K.cnt), dim3(256), 0, c->stream, R);
+        RS_HIP(hipGetLastError());
+        A.rows_tab = (const float*)K.base;
+        A.outside = (unsigned long long*)c->rect_count.p + K.f0;
+        A.src = K.src[0]; A.src_pitch = K.src_pitch[0]; A.src_stride = K.src_stride[0];
+        A.dst = K.dst[0]; A.dst_pitch = K.dst_pitch[0]; A.dst_stride = K.dst_stride[0];
+        launch(A, K.f0, K.cnt);
+        RS_HIP(hipGetLastError());
         return 0;
-    };
-    bool used[2] = {false, false};
-    int slot = 0;
-    if (upload(0, false, 0, std::min(chunk, n_frames))) return 1;
-    for (uint32_t f0 = 0; f0 < n_frames;) {
-        const uint32_t cnt = std::min(chunk, n_frames - f0);
-        uint8_t* base = (uint8_t*)c->rect_slot[slot].p;
-        uint8_t* s_in = base + tab_bytes;
-        uint8_t* s_out = s_in + (dev_in ? 0 : (size_t)chunk * px_in);
-        RS_HIP(hipStreamWaitEvent(c->stream, c->trk_up[slot], 0));
-        R.times = (const double*)c->rect_times.p + f0;
-        R.targets = (const double*)c->stab_targets.p + (size_t)f0 * 4;
-        R.rows_tab = (float*)base;
-        R.n_frames = cnt;
-        hipLaunchKernelGGL(stabilize_rows_kernel, dim3((h + 1 + 255) / 256, cnt), dim3(256), 0, c->stream, R);
-        RS_HIP(hipGetLastError());
-        A.rows_tab = (const float*)base;
-        A.outside = (unsigned long long*)c->rect_count.p + f0;
-        if (dev_in) { A.src = frames + (size_t)f0 * frame_stride; A.src_pitch = pitch; A.src_stride = frame_stride; }
-        else { A.src = s_in; A.src_pitch = w; A.src_stride = px_in; }
-        if (dev_out) { A.dst = out + (size_t)f0 * out_stride; A.dst_pitch = out_pitch; A.dst_stride = out_stride; }
-        else { A.dst = s_out; A.dst_pitch = ow; A.dst_stride = px_out; }
-        launch(A, f0, cnt);
-        RS_HIP(hipGetLastError());
-        RS_HIP(hipEventRecord(c->trk_k[slot], c->stream));
-        used[slot] = true;
-        const uint32_t next = f0 + cnt;
-        if (next < n_frames && upload(slot ^ 1, used[slot ^ 1], next, std::min(chunk, n_frames - next))) return 1;
-        if (!dev_out) {
-            RS_HIP(hipStreamWaitEvent(c->copy_stream, c->trk_k[slot], 0));
-            if (rect_copy(c, out + (size_t)f0 * out_stride, out_pitch, out_stride, s_out, ow, px_out, ow, oh, cnt)) return 1;
-        }
-        f0 = next;
-        slot ^= 1;
-    }
-    if (n_outside) RS_HIP(hipMemcpyAsync(n_outside, c->rect_count.p, (size_t)n_frames * 8, hipMemcpyDeviceToHost, c->stream));
-    RS_HIP(hipStreamSynchronize(c->copy_stream));
+    });
+}
+
+// One frame's source positions, rship_stabilize_map's and a chroma plane's: the rows of the frame whose time is
+// c->rect_times[time_at] against the target in c->stab_targets, the map of g's output camera from `rays`, and its download
+// where map_xy is host memory
+int stab_map_run(rship_ctx* c, const rship_stabilize_cfg* g, const DevBuf& rays, size_t time_at, float* map_xy, bool on_dev) {
+    const uint32_t h = g->height;
+    const size_t n = (size_t)g->out_width * g->out_height;
+    if (ensure(c, c->rect_slot[0], (size_t)(h + 1) * 9 * sizeof(float)) || (!on_dev && ensure(c, c->rect_tmp, n * sizeof(float2)))) return 1;
+    StabRowsArgs R = stab_rows_args(c, g);
+    R.times = (const double*)c->rect_times.p + time_at;
+    R.targets = (const double*)c->stab_targets.p;
+    R.rows_tab = (float*)c->rect_slot[0].p;
+    R.n_frames = 1;
+    hipLaunchKernelGGL(stabilize_rows_kernel, dim3((h + 1 + 255) / 256, 1), dim3(256), 0, c->stream, R);
+    RS_HIP(hipGetLastError());
+    StabArgs A = stab_args(c, g);
+    A.rays = (const float4*)rays.p;
+    A.rows_tab = (const float*)c->rect_slot[0].p;
+    A.map = on_dev ? (float2*)map_xy : (float2*)c->rect_tmp.p;
+    stab_launch<true>(c, g, A, 1);
+    RS_HIP(hipGetLastError());
+    if (!on_dev) RS_HIP(hipMemcpyAsync(map_xy, c->rect_tmp.p, n * sizeof(float2), hipMemcpyDeviceToHost, c->stream));
     return sync_stream(c);
 }
 
@@ -4161,27 +4179,10 @@ int rship_stabilize_map(rship_ctx* c, double frame_time, const double* target, c
     if (!map_xy) return set_err(c, "stabilize: null pointer");
     bool on_dev = false;
     if (rect_pointer(c, map_xy, "the map", &on_dev, "stabilize")) return 1;
-    const uint32_t h = cfg->height;
-    const size_t n = (size_t)cfg->out_width * cfg->out_height;
-    if (ensure(c, c->rect_slot[0], (size_t)(h + 1) * 9 * sizeof(float)) || ensure(c, c->rect_times, 8) ||
-        (!on_dev && ensure(c, c->rect_tmp, n * sizeof(float2))))
-        return 1;
+    if (ensure(c, c->rect_times, 8)) return 1;
     RS_HIP(hipMemcpy(c->rect_times.p, &frame_time, 8, hipMemcpyHostToDevice));
     if (stab_fill_targets(c, cfg, target, 1) || stab_rays(c, cfg)) return 1;
-    StabRowsArgs R = stab_rows_args(c, cfg);
-    R.times = (const double*)c->rect_times.p;
-    R.targets = (const double*)c->stab_targets.p;
-    R.rows_tab = (float*)c->rect_slot[0].p;
-    R.n_frames = 1;
-    hipLaunchKernelGGL(stabilize_rows_kernel, dim3((h + 1 + 255) / 256, 1), dim3(256), 0, c->stream, R);
-    RS_HIP(hipGetLastError());
-    StabArgs A = stab_args(c, cfg);
-    A.rows_tab = (const float*)c->rect_slot[0].p;
-    A.map = on_dev ? (float2*)map_xy : (float2*)c->rect_tmp.p;
-    stab_launch<true>(c, cfg, A, 1);
-    RS_HIP(hipGetLastError());
-    if (!on_dev) RS_HIP(hipMemcpyAsync(map_xy, c->rect_tmp.p, n * sizeof(float2), hipMemcpyDeviceToHost, c->stream));
-    return sync_stream(c);
+    return stab_map_run(c, cfg, c->rect_rays, 0, map_xy, on_dev);
 }
 
 int rship_stabilize_coverage(rship_ctx* c, const double* frame_times, uint32_t n_frames, const double* targets,
@@ -4320,11 +4321,7 @@ int rship_zoom_frames(rship_ctx* c, const uint8_t* frames, uint32_t n_frames, si
                            false, [&](const StabArgs& A, uint32_t f0, uint32_t cnt) {
                                Z.S = A;
                                Z.cams = (const double*)c->stab_zooms.p + 2 * (size_t)f0;
-                               const dim3 grid((cfg->out_width + kRectTW - 1) / kRectTW, (cfg->out_height + kRectTH - 1) / kRectTH, cnt);
-                               if (cfg->camera == 0 && cfg->filter == 0) hipLaunchKernelGGL((zoom_render_kernel<0, 0>), grid, dim3(256), 0, c->stream, Z);
-                               else if (cfg->camera == 0) hipLaunchKernelGGL((zoom_render_kernel<0, 1>), grid, dim3(256), 0, c->stream, Z);
-                               else if (cfg->filter == 0) hipLaunchKernelGGL((zoom_render_kernel<1, 0>), grid, dim3(256), 0, c->stream, Z);
-                               else hipLaunchKernelGGL((zoom_render_kernel<1, 1>), grid, dim3(256), 0, c->stream, Z);
+                               camfilt_launch<PickZoom>(c, cfg->camera, cfg->filter, stab_grid(cfg, cnt), Z);
                            });
 }
 
@@ -4409,11 +4406,6 @@ int rship_limit_fit(rship_ctx* c, const double* frame_times, uint32_t n_frames, 
 
 namespace {
 
-struct ColorPlane {
-    size_t row_bytes;
-    uint32_t rows;
-};
-
 // the 16-bit formats (include/rssync_color16.h): GRAY16 16, P010 17, P016 18, I010 19
 bool color_is_16(int format) { return format >= 16 && format <= 19; }
 
@@ -4421,7 +4413,7 @@ bool color_is_16(int format) { return format >= 16 && format <= 19; }
 int color_sibling(int format) { return format == 16 ? 0 : (format == 17 || format == 18) ? 1 : format == 19 ? 2 : format; }
 
 // the planes of a width x height frame -> their number; a 16-bit format's rows are twice its sibling's bytes
-int color_planes(int format, uint32_t w, uint32_t h, ColorPlane* pl) {
+int color_planes(int format, uint32_t w, uint32_t h, rs::FramePlane* pl) {
     const size_t b = color_is_16(format) ? 2 : 1;
     switch (color_sibling(format)) {
     case 0: pl[0] = {b * w, h}; return 1;
@@ -4481,7 +4473,7 @@ struct ColorLaunch {
     uint32_t fill16_y, fill16_uv;
 };
 
-// The chunk pipeline of the colour frames: rship_color_frames' and rship_colorzoom_frames'.  launch(K, f0, cnt) enqueues the
+// The frames of rship_color_frames and rship_colorzoom_frames through frame_pipeline.  launch(K, f0, cnt) enqueues the
 // kernel that renders the chunk's cnt frames, the first of which is frame f0 of the call; ray_maps: the cached ray maps of
 // cfg's output cameras are needed.
 template <class Launch>
@@ -4495,10 +4487,10 @@ int color_frames_run(rship_ctx* c, const rship_color_image* in, uint32_t n_frame
     if (!wide) L.fill = cfg->fill[0]; // (the 16-bit kernels take their fills as arguments of their own)
     const bool yuv = color_is_yuv(cfg->format);
     const uint32_t h = L.height, ow = L.out_width, oh = L.out_height, hc = yuv ? h / 2 : 0;
-    ColorPlane pi[3] = {}, po[3] = {};
+    rs::FrameLayout q;
+    rs::FramePlane *pi = q.in, *po = q.out;
     const int np = color_planes(cfg->format, L.width, h, pi);
     color_planes(cfg->format, ow, oh, po);
-    size_t in_bytes = 0, out_bytes = 0;
     for (int k = 0; k < np; ++k) {
         if (!in->plane[k] || !out->plane[k]) return set_err(c, "color: null pointer");
         if (wide && (((uintptr_t)in->plane[k] | (uintptr_t)out->plane[k] | in->pitch[k] | out->pitch[k]) & 1u ||
@@ -4507,25 +4499,18 @@ int color_frames_run(rship_ctx* c, const rship_color_image* in, uint32_t n_frame
         if (in->pitch[k] < pi[k].row_bytes || out->pitch[k] < po[k].row_bytes ||
             (n_frames > 1 && (in->stride[k] < in->pitch[k] * pi[k].rows || out->stride[k] < out->pitch[k] * po[k].rows)))
             return set_err(c, "color: pitch or frame stride too small");
-        in_bytes += pi[k].row_bytes * pi[k].rows;
-        out_bytes += po[k].row_bytes * po[k].rows;
     }
     bool dev_in = false, dev_out = false;
     if (color_kind(c, in, np, "the frames", &dev_in) || color_kind(c, out, np, "the stabilised frames", &dev_out)) return 1;
     // a frame's bytes: both row tables and every plane that has to pass through the slot
-    const size_t tab = (size_t)(h + 1) * 9 * sizeof(float), tab_c = yuv ? (size_t)(hc + 1) * 9 * sizeof(float) : 0;
-    const size_t per_frame = tab + tab_c + (dev_in ? 0 : in_bytes) + (dev_out ? 0 : out_bytes);
-    const size_t budget = budget_bytes ? budget_bytes : kRectBudget;
-    const uint32_t chunk = (uint32_t)std::min<uint64_t>(std::min(n_frames, kRectMaxChunk), std::max<uint64_t>(1, budget / 2 / per_frame));
-    const size_t tab_bytes = ((size_t)chunk * tab + 255) / 256 * 256, tab_c_bytes = ((size_t)chunk * tab_c + 255) / 256 * 256;
-    const size_t slot_bytes = tab_bytes + tab_c_bytes + (size_t)chunk * (per_frame - tab - tab_c);
-    // where the chunk's planes lie in a slot: every plane packed, [chunk][rows][row bytes]
-    size_t off_in[3] = {}, off_out[3] = {}, off = tab_bytes + tab_c_bytes;
-    for (int k = 0; k < np && !dev_in; ++k) { off_in[k] = off; off += (size_t)chunk * pi[k].row_bytes * pi[k].rows; }
-    for (int k = 0; k < np && !dev_out; ++k) { off_out[k] = off; off += (size_t)chunk * po[k].row_bytes * po[k].rows; }
-    for (uint32_t s = 0; s < (n_frames > chunk ? 2u : 1u); ++s)
-        if (ensure(c, c->rect_slot[s], slot_bytes)) return 1;
-    if (ensure(c, c->rect_times, (size_t)n_frames * 16) || ensure(c, c->rect_count, (size_t)n_frames * 16) || rect_events(c)) return 1;
+    q.n_frames = n_frames;
+    q.budget = budget_bytes;
+    q.tab[0] = (size_t)(h + 1) * 9 * sizeof(float);
+    q.tab[1] = yuv ? (size_t)(hc + 1) * 9 * sizeof(float) : 0;
+    q.n_in = dev_in ? 0 : np;
+    q.n_out = dev_out ? 0 : np;
+    const rs::FramePlan P = rs::plan_frames(q);
+    if (ensure(c, c->rect_times, (size_t)n_frames * 16) || ensure(c, c->rect_count, (size_t)n_frames * 16)) return 1;
     // the frames' times, then the chroma planes'; the filled pixels of plane 0, then the filled chroma samples
     std::vector<double> times(2 * (size_t)n_frames);
     for (uint32_t k = 0; k < n_frames; ++k) {
@@ -4561,73 +4546,52 @@ int color_frames_run(rship_ctx* c, const rship_color_image* in, uint32_t n_frame
     K.fill16_y = (uint32_t)cfg->fill[0] << sh16;
     K.fill16_uv = (uint32_t)cfg->fill[1] << sh16 | (uint32_t)cfg->fill[2] << (16 + sh16);
     if (wide) A.fill = 0;
-    // the chunk pipeline of rship_rectify_frames: chunk j in slot j & 1, uploads and downloads on the copy stream
-    auto upload = [&](int slot, bool reused, uint32_t f0, uint32_t cnt) -> int {
-        if (reused) RS_HIP(hipStreamWaitEvent(c->copy_stream, c->trk_k[slot], 0));
-        for (int k = 0; k < np && !dev_in; ++k)
-            if (rect_copy(c, (uint8_t*)c->rect_slot[slot].p + off_in[k], pi[k].row_bytes, pi[k].row_bytes * pi[k].rows,
-                          in->plane[k] + (size_t)f0 * in->stride[k], in->pitch[k], in->stride[k], (uint32_t)pi[k].row_bytes, pi[k].rows, cnt))
-                return 1;
-        RS_HIP(hipEventRecord(c->trk_up[slot], c->copy_stream));
-        return 0;
-    };
-    bool used[2] = {false, false};
-    int slot = 0;
-    if (upload(0, false, 0, std::min(chunk, n_frames))) return 1;
-    for (uint32_t f0 = 0; f0 < n_frames;) {
-        const uint32_t cnt = std::min(chunk, n_frames - f0);
-        uint8_t* base = (uint8_t*)c->rect_slot[slot].p;
-        RS_HIP(hipStreamWaitEvent(c->stream, c->trk_up[slot], 0));
-        R.times = (const double*)c->rect_times.p + f0;
-        R.times_c = (const double*)c->rect_times.p + n_frames + f0;
-        R.targets = (const double*)c->stab_targets.p + (size_t)f0 * 4;
-        R.rows_tab = (float*)base;
-        R.rows_tab_c = (float*)(base + tab_bytes);
-        R.n_frames = cnt;
-        hipLaunchKernelGGL(color_rows_kernel, dim3((h + 1 + (yuv ? hc + 1 : 0) + 255) / 256, cnt), dim3(256), 0, c->stream, R);
-        RS_HIP(hipGetLastError());
-        A.luma.rows_tab = (const float*)base;
-        A.chroma.rows_tab = (const float*)(base + tab_bytes);
-        A.outside = (unsigned long long*)c->rect_count.p + f0;
-        A.outside_c = (unsigned long long*)c->rect_count.p + n_frames + f0;
-        for (int k = 0; k < np; ++k) {
-            if (dev_in) { A.src[k] = in->plane[k] + (size_t)f0 * in->stride[k]; A.src_pitch[k] = in->pitch[k]; A.src_stride[k] = in->stride[k]; }
-            else { A.src[k] = base + off_in[k]; A.src_pitch[k] = pi[k].row_bytes; A.src_stride[k] = pi[k].row_bytes * pi[k].rows; }
-            if (dev_out) { A.dst[k] = out->plane[k] + (size_t)f0 * out->stride[k]; A.dst_pitch[k] = out->pitch[k]; A.dst_stride[k] = out->stride[k]; }
-            else { A.dst[k] = base + off_out[k]; A.dst_pitch[k] = po[k].row_bytes; A.dst_stride[k] = po[k].row_bytes * po[k].rows; }
-        }
-        if (cfg->format == 0) {
-            G.rows_tab = A.luma.rows_tab;
-            G.outside = A.outside;
-            G.src = A.src[0]; G.src_pitch = A.src_pitch[0]; G.src_stride = A.src_stride[0];
-            G.dst = A.dst[0]; G.dst_pitch = A.dst_pitch[0]; G.dst_stride = A.dst_stride[0];
-        }
-        launch(K, f0, cnt);
-        RS_HIP(hipGetLastError());
-        RS_HIP(hipEventRecord(c->trk_k[slot], c->stream));
-        used[slot] = true;
-        const uint32_t next = f0 + cnt;
-        if (next < n_frames && upload(slot ^ 1, used[slot ^ 1], next, std::min(chunk, n_frames - next))) return 1;
-        if (!dev_out) {
-            RS_HIP(hipStreamWaitEvent(c->copy_stream, c->trk_k[slot], 0));
-            for (int k = 0; k < np; ++k)
-                if (rect_copy(c, out->plane[k] + (size_t)f0 * out->stride[k], out->pitch[k], out->stride[k], base + off_out[k], po[k].row_bytes,
-                              po[k].row_bytes * po[k].rows, (uint32_t)po[k].row_bytes, po[k].rows, cnt))
-                    return 1;
-        }
-        f0 = next;
-        slot ^= 1;
-    }
+    // the filled pixels of plane 0 and the filled chroma samples come back as two runs and go to the caller in pairs
     std::vector<uint64_t> counts(n_outside ? 2 * (size_t)n_frames : 0);
-    if (n_outside) RS_HIP(hipMemcpyAsync(counts.data(), c->rect_count.p, counts.size() * 8, hipMemcpyDeviceToHost, c->stream));
-    RS_HIP(hipStreamSynchronize(c->copy_stream));
-    if (sync_stream(c)) return 1;
+    if (frame_pipeline(c, P, np, *in, *out, n_outside ? counts.data() : nullptr, counts.size(), [&](const FrameChunk& C) -> int {
+            const uint32_t f0 = C.f0, cnt = C.cnt;
+            R.times = (const double*)c->rect_times.p + f0;
+            R.times_c = (const double*)c->rect_times.p + n_frames + f0;
+            R.targets = (const double*)c->stab_targets.p + (size_t)f0 * 4;
+            R.rows_tab = (float*)(C.base + P.off_tab[0]);
+            R.rows_tab_c = (float*)(C.base + P.off_tab[1]);
+            R.n_frames = cnt;
+            hipLaunchKernelGGL(color_rows_kernel, dim3((h + 1 + (yuv ? hc + 1 : 0) + 255) / 256, cnt), dim3(256), 0, c->stream, R);
+            RS_HIP(hipGetLastError());
+            A.luma.rows_tab = R.rows_tab;
+            A.chroma.rows_tab = R.rows_tab_c;
+            A.outside = (unsigned long long*)c->rect_count.p + f0;
+            A.outside_c = (unsigned long long*)c->rect_count.p + n_frames + f0;
+            for (int k = 0; k < np; ++k) {
+                A.src[k] = C.src[k]; A.src_pitch[k] = C.src_pitch[k]; A.src_stride[k] = C.src_stride[k];
+                A.dst[k] = C.dst[k]; A.dst_pitch[k] = C.dst_pitch[k]; A.dst_stride[k] = C.dst_stride[k];
+            }
+            if (cfg->format == 0) {
+                G.rows_tab = A.luma.rows_tab;
+                G.outside = A.outside;
+                G.src = A.src[0]; G.src_pitch = A.src_pitch[0]; G.src_stride = A.src_stride[0];
+                G.dst = A.dst[0]; G.dst_pitch = A.dst_pitch[0]; G.dst_stride = A.dst_stride[0];
+            }
+            launch(K, f0, cnt);
+            RS_HIP(hipGetLastError());
+            return 0;
+        }))
+        return 1;
     for (size_t k = 0; k < counts.size() / 2; ++k) {
         n_outside[2 * k] = counts[k];
         n_outside[2 * k + 1] = counts[n_frames + k];
     }
     return 0;
 }
+
+// F: the linear kernel of a format, or its cubic sibling of kernels/resample.hpp
+template <int C, int F> struct PickNv12 { static constexpr auto kernel = F ? bicubic_yuv_kernel<C, true> : color_yuv_kernel<C, true>; };
+template <int C, int F> struct PickI420 { static constexpr auto kernel = F ? bicubic_yuv_kernel<C, false> : color_yuv_kernel<C, false>; };
+template <int C, int F> struct PickRgba { static constexpr auto kernel = F ? bicubic_rgba_kernel<C> : color_rgba_kernel<C>; };
+template <int C, int F> struct PickGray16 { static constexpr auto kernel = F ? bicubic16_gray_kernel<C> : color16_gray_kernel<C>; };
+template <int C, int F> struct PickP010 { static constexpr auto kernel = F ? bicubic16_yuv_kernel<C, true, 6> : color16_yuv_kernel<C, true, 6>; };
+template <int C, int F> struct PickP016 { static constexpr auto kernel = F ? bicubic16_yuv_kernel<C, true, 0> : color16_yuv_kernel<C, true, 0>; };
+template <int C, int F> struct PickI010 { static constexpr auto kernel = F ? bicubic16_yuv_kernel<C, false, 0> : color16_yuv_kernel<C, false, 0>; };
 
 } // namespace
 
@@ -4645,53 +4609,15 @@ int rship_color_frames(rship_ctx* c, const rship_color_image* in, uint32_t n_fra
         const ColorArgs& A = K.A;
         const dim3 grid((ow + kRectTW - 1) / kRectTW, (oh + kRectTH - 1) / kRectTH, cnt);
         const dim3 grid_c((ow / 2 + kRectTW - 1) / kRectTW, (oh / 2 + kRectTH - 1) / kRectTH, cnt);
-        const bool lens_cam = L.camera == 0, cubic = L.filter == 1; // cubic: the siblings of kernels/resample.hpp
         switch (cfg->format) {
-        case 0:
-            stab_launch<false>(c, &L, K.G, cnt);
-            break;
-        case 1:
-            if (cubic && lens_cam) hipLaunchKernelGGL((bicubic_yuv_kernel<0, true>), grid_c, dim3(256), 0, c->stream, A);
-            else if (cubic) hipLaunchKernelGGL((bicubic_yuv_kernel<1, true>), grid_c, dim3(256), 0, c->stream, A);
-            else if (lens_cam) hipLaunchKernelGGL((color_yuv_kernel<0, true>), grid_c, dim3(256), 0, c->stream, A);
-            else hipLaunchKernelGGL((color_yuv_kernel<1, true>), grid_c, dim3(256), 0, c->stream, A);
-            break;
-        case 2:
-            if (cubic && lens_cam) hipLaunchKernelGGL((bicubic_yuv_kernel<0, false>), grid_c, dim3(256), 0, c->stream, A);
-            else if (cubic) hipLaunchKernelGGL((bicubic_yuv_kernel<1, false>), grid_c, dim3(256), 0, c->stream, A);
-            else if (lens_cam) hipLaunchKernelGGL((color_yuv_kernel<0, false>), grid_c, dim3(256), 0, c->stream, A);
-            else hipLaunchKernelGGL((color_yuv_kernel<1, false>), grid_c, dim3(256), 0, c->stream, A);
-            break;
-        case 3:
-            if (cubic && lens_cam) hipLaunchKernelGGL((bicubic_rgba_kernel<0>), grid, dim3(256), 0, c->stream, A);
-            else if (cubic) hipLaunchKernelGGL((bicubic_rgba_kernel<1>), grid, dim3(256), 0, c->stream, A);
-            else if (lens_cam) hipLaunchKernelGGL((color_rgba_kernel<0>), grid, dim3(256), 0, c->stream, A);
-            else hipLaunchKernelGGL((color_rgba_kernel<1>), grid, dim3(256), 0, c->stream, A);
-            break;
-        case 16:
-            if (cubic && lens_cam) hipLaunchKernelGGL((bicubic16_gray_kernel<0>), grid, dim3(256), 0, c->stream, A, K.fill16_y);
-            else if (cubic) hipLaunchKernelGGL((bicubic16_gray_kernel<1>), grid, dim3(256), 0, c->stream, A, K.fill16_y);
-            else if (lens_cam) hipLaunchKernelGGL((color16_gray_kernel<0>), grid, dim3(256), 0, c->stream, A, K.fill16_y);
-            else hipLaunchKernelGGL((color16_gray_kernel<1>), grid, dim3(256), 0, c->stream, A, K.fill16_y);
-            break;
-        case 17:
-            if (cubic && lens_cam) hipLaunchKernelGGL((bicubic16_yuv_kernel<0, true, 6>), grid_c, dim3(256), 0, c->stream, A, K.fill16_y, K.fill16_uv);
-            else if (cubic) hipLaunchKernelGGL((bicubic16_yuv_kernel<1, true, 6>), grid_c, dim3(256), 0, c->stream, A, K.fill16_y, K.fill16_uv);
-            else if (lens_cam) hipLaunchKernelGGL((color16_yuv_kernel<0, true, 6>), grid_c, dim3(256), 0, c->stream, A, K.fill16_y, K.fill16_uv);
-            else hipLaunchKernelGGL((color16_yuv_kernel<1, true, 6>), grid_c, dim3(256), 0, c->stream, A, K.fill16_y, K.fill16_uv);
-            break;
-        case 18:
-            if (cubic && lens_cam) hipLaunchKernelGGL((bicubic16_yuv_kernel<0, true, 0>), grid_c, dim3(256), 0, c->stream, A, K.fill16_y, K.fill16_uv);
-            else if (cubic) hipLaunchKernelGGL((bicubic16_yuv_kernel<1, true, 0>), grid_c, dim3(256), 0, c->stream, A, K.fill16_y, K.fill16_uv);
-            else if (lens_cam) hipLaunchKernelGGL((color16_yuv_kernel<0, true, 0>), grid_c, dim3(256), 0, c->stream, A, K.fill16_y, K.fill16_uv);
-            else hipLaunchKernelGGL((color16_yuv_kernel<1, true, 0>), grid_c, dim3(256), 0, c->stream, A, K.fill16_y, K.fill16_uv);
-            break;
-        case 19:
-            if (cubic && lens_cam) hipLaunchKernelGGL((bicubic16_yuv_kernel<0, false, 0>), grid_c, dim3(256), 0, c->stream, A, K.fill16_y, K.fill16_uv);
-            else if (cubic) hipLaunchKernelGGL((bicubic16_yuv_kernel<1, false, 0>), grid_c, dim3(256), 0, c->stream, A, K.fill16_y, K.fill16_uv);
-            else if (lens_cam) hipLaunchKernelGGL((color16_yuv_kernel<0, false, 0>), grid_c, dim3(256), 0, c->stream, A, K.fill16_y, K.fill16_uv);
-            else hipLaunchKernelGGL((color16_yuv_kernel<1, false, 0>), grid_c, dim3(256), 0, c->stream, A, K.fill16_y, K.fill16_uv);
-            break;
+        case 0: stab_launch<false>(c, &L, K.G, cnt); break;
+        case 1: camfilt_launch<PickNv12>(c, L.camera, L.filter, grid_c, A); break;
+        case 2: camfilt_launch<PickI420>(c, L.camera, L.filter, grid_c, A); break;
+        case 3: camfilt_launch<PickRgba>(c, L.camera, L.filter, grid, A); break;
+        case 16: camfilt_launch<PickGray16>(c, L.camera, L.filter, grid, A, K.fill16_y); break;
+        case 17: camfilt_launch<PickP010>(c, L.camera, L.filter, grid_c, A, K.fill16_y, K.fill16_uv); break;
+        case 18: camfilt_launch<PickP016>(c, L.camera, L.filter, grid_c, A, K.fill16_y, K.fill16_uv); break;
+        case 19: camfilt_launch<PickI010>(c, L.camera, L.filter, grid_c, A, K.fill16_y, K.fill16_uv); break;
         }
     });
 }
@@ -4709,29 +4635,11 @@ int rship_color_map(rship_ctx* c, int plane, double frame_time, const double* ta
     bool on_dev = false;
     if (rect_pointer(c, map_xy, "the map", &on_dev, "color")) return 1;
     const rship_stabilize_cfg* g = &cfg->chroma;
-    const uint32_t h = g->height;
-    const size_t n = (size_t)g->out_width * g->out_height;
-    if (ensure(c, c->rect_slot[0], (size_t)(h + 1) * 9 * sizeof(float)) || ensure(c, c->rect_times, 16) ||
-        (!on_dev && ensure(c, c->rect_tmp, n * sizeof(float2))))
-        return 1;
+    if (ensure(c, c->rect_times, 16)) return 1;
     const double times[2] = {frame_time, frame_time + cfg->chroma_time};
     RS_HIP(hipMemcpy(c->rect_times.p, times, 16, hipMemcpyHostToDevice));
     if (stab_fill_targets(c, &cfg->luma, target, 1) || stab_rays(c, g, true)) return 1;
-    StabRowsArgs R = stab_rows_args(c, g);
-    R.times = (const double*)c->rect_times.p + 1;
-    R.targets = (const double*)c->stab_targets.p;
-    R.rows_tab = (float*)c->rect_slot[0].p;
-    R.n_frames = 1;
-    hipLaunchKernelGGL(stabilize_rows_kernel, dim3((h + 1 + 255) / 256, 1), dim3(256), 0, c->stream, R);
-    RS_HIP(hipGetLastError());
-    StabArgs A = stab_args(c, g);
-    A.rays = (const float4*)c->rect_rays_c.p;
-    A.rows_tab = (const float*)c->rect_slot[0].p;
-    A.map = on_dev ? (float2*)map_xy : (float2*)c->rect_tmp.p;
-    stab_launch<true>(c, g, A, 1);
-    RS_HIP(hipGetLastError());
-    if (!on_dev) RS_HIP(hipMemcpyAsync(map_xy, c->rect_tmp.p, n * sizeof(float2), hipMemcpyDeviceToHost, c->stream));
-    return sync_stream(c);
+    return stab_map_run(c, g, c->rect_rays_c, 1, map_xy, on_dev);
 }
 
 } // extern "C"
@@ -4741,14 +4649,6 @@ int rship_color_map(rship_ctx* c, int plane, double frame_time, const double* ta
 // The colour front's pipeline with a camera per frame, as rship_zoom_frames is the stabiliser's.
 
 namespace {
-
-template <template <int, int> class Pick>
-void percam_launch2(rship_ctx* c, bool lens_cam, bool cubic, dim3 grid, const PercamArgs& P) {
-    if (lens_cam && !cubic) hipLaunchKernelGGL((Pick<0, 0>::kernel), grid, dim3(256), 0, c->stream, P);
-    else if (lens_cam) hipLaunchKernelGGL((Pick<0, 1>::kernel), grid, dim3(256), 0, c->stream, P);
-    else if (!cubic) hipLaunchKernelGGL((Pick<1, 0>::kernel), grid, dim3(256), 0, c->stream, P);
-    else hipLaunchKernelGGL((Pick<1, 1>::kernel), grid, dim3(256), 0, c->stream, P);
-}
 
 template <int C, int F> struct PercamNv12 { static constexpr auto kernel = percam_yuv8_kernel<C, true, F>; };
 template <int C, int F> struct PercamI420 { static constexpr auto kernel = percam_yuv8_kernel<C, false, F>; };
@@ -4809,14 +4709,10 @@ int rship_colorzoom_frames(rship_ctx* c, const rship_color_image* in, uint32_t n
                             [&](const ColorLaunch& K, uint32_t f0, uint32_t cnt) {
         const dim3 grid((ow + kRectTW - 1) / kRectTW, (oh + kRectTH - 1) / kRectTH, cnt);
         const dim3 grid_c((ow / 2 + kRectTW - 1) / kRectTW, (oh / 2 + kRectTH - 1) / kRectTH, cnt);
-        const bool lens_cam = L.camera == 0, cubic = L.filter == 1;
         if (cfg->format == 0) {
             Z.S = K.G;
             Z.cams = (const double*)c->stab_zooms.p + 2 * (size_t)f0;
-            if (lens_cam && !cubic) hipLaunchKernelGGL((zoom_render_kernel<0, 0>), grid, dim3(256), 0, c->stream, Z);
-            else if (lens_cam) hipLaunchKernelGGL((zoom_render_kernel<0, 1>), grid, dim3(256), 0, c->stream, Z);
-            else if (!cubic) hipLaunchKernelGGL((zoom_render_kernel<1, 0>), grid, dim3(256), 0, c->stream, Z);
-            else hipLaunchKernelGGL((zoom_render_kernel<1, 1>), grid, dim3(256), 0, c->stream, Z);
+            camfilt_launch<PickZoom>(c, L.camera, L.filter, grid, Z);
             return;
         }
         P.C = K.A;
@@ -4824,13 +4720,13 @@ int rship_colorzoom_frames(rship_ctx* c, const rship_color_image* in, uint32_t n
         P.fill_y = K.fill16_y;
         P.fill_uv = K.fill16_uv;
         switch (cfg->format) {
-        case 1: percam_launch2<PercamNv12>(c, lens_cam, cubic, grid_c, P); break;
-        case 2: percam_launch2<PercamI420>(c, lens_cam, cubic, grid_c, P); break;
-        case 3: percam_launch2<PercamRgba>(c, lens_cam, cubic, grid, P); break;
-        case 16: percam_launch2<PercamGray16>(c, lens_cam, cubic, grid, P); break;
-        case 17: percam_launch2<PercamP010>(c, lens_cam, cubic, grid_c, P); break;
-        case 18: percam_launch2<PercamP016>(c, lens_cam, cubic, grid_c, P); break;
-        case 19: percam_launch2<PercamI010>(c, lens_cam, cubic, grid_c, P); break;
+        case 1: camfilt_launch<PercamNv12>(c, L.camera, L.filter, grid_c, P); break;
+        case 2: camfilt_launch<PercamI420>(c, L.camera, L.filter, grid_c, P); break;
+        case 3: camfilt_launch<PercamRgba>(c, L.camera, L.filter, grid, P); break;
+        case 16: camfilt_launch<PercamGray16>(c, L.camera, L.filter, grid, P); break;
+        case 17: camfilt_launch<PercamP010>(c, L.camera, L.filter, grid_c, P); break;
+        case 18: camfilt_launch<PercamP016>(c, L.camera, L.filter, grid_c, P); break;
+        case 19: camfilt_launch<PercamI010>(c, L.camera, L.filter, grid_c, P); break;
         }
     });
 }
@@ -4838,9 +4734,13 @@ int rship_colorzoom_frames(rship_ctx* c, const rship_color_image* in, uint32_t n
 } // extern "C"
 
 // ===========================================================================
-// infill (kernels/infill.hpp; declared in infill_hip.h, called by infill_api.cpp).  The chunk pipeline of stab_frames_run
-// with a halo: a chunk of output frames reads its own input frames and `radius` more on each side.  Host frames: a slot
-// holds the chunk with its halo, uploaded anew for every chunk.  Device frames: the kernel reads the neighbours in place.
+// infill (kernels/infill.hpp; declared in infill_hip.h, called by infill_api.cpp).  frame_pipeline with a halo: a chunk
+// of output frames reads its own input frames and `radius` more on each side.  Host frames: a slot holds the chunk with
+// its halo, uploaded anew for every chunk.  Device frames: the kernel reads the neighbours in place.
+
+namespace {
+template <int C, int F> struct PickInfill { static constexpr auto kernel = infill_kernel<C, F>; };
+} // namespace
 
 extern "C" {
 
@@ -4859,18 +4759,9 @@ int rship_infill_frames(rship_ctx* c, const uint8_t* frames, uint32_t n_frames, 
     bool dev_in = false, dev_out = false;
     if (rect_pointer(c, frames, "the frames", &dev_in, "stabilize") || rect_pointer(c, out, "the stabilised frames", &dev_out, "stabilize")) return 1;
     // the chunk: per output frame its tables, its input and its output; per slot the halo's input frames besides
-    const size_t px_in = (size_t)w * h, px_out = (size_t)ow * oh, tab = (size_t)(h + 1) * 9 * sizeof(float);
-    const size_t per_frame = places * tab + (dev_in ? 0 : px_in) + (dev_out ? 0 : px_out);
-    const size_t halo = dev_in ? 0 : (size_t)std::min<uint64_t>(2 * r, n_frames - 1) * px_in;
-    const size_t budget = (budget_bytes ? budget_bytes : kRectBudget) / 2;
-    const uint32_t chunk = (uint32_t)std::min<uint64_t>(std::min(n_frames, kRectMaxChunk), std::max<uint64_t>(1, (budget > halo ? budget - halo : 0) / per_frame));
-    const uint32_t held = (uint32_t)std::min<uint64_t>(n_frames, (uint64_t)chunk + 2 * r); // input frames of a slot
-    const size_t tab_bytes = ((size_t)chunk * places * tab + 255) / 256 * 256;
-    const size_t slot_bytes = tab_bytes + (dev_in ? 0 : (size_t)held * px_in) + (dev_out ? 0 : (size_t)chunk * px_out);
-    for (uint32_t s = 0; s < (n_frames > chunk ? 2u : 1u); ++s)
-        if (ensure(c, c->rect_slot[s], slot_bytes)) return 1;
+    const rs::FramePlan P = gray_plan(n_frames, budget_bytes, places, r, w, h, dev_in, ow, oh, dev_out);
     // (the counts: [0, n_frames) the filled pixels, [n_frames, 2 n_frames) the borrowed ones)
-    if (ensure(c, c->rect_times, (size_t)n_frames * 8) || ensure(c, c->rect_count, (size_t)n_frames * 16) || rect_events(c)) return 1;
+    if (ensure(c, c->rect_times, (size_t)n_frames * 8) || ensure(c, c->rect_count, (size_t)n_frames * 16)) return 1;
     RS_HIP(hipMemcpy(c->rect_times.p, frame_times, (size_t)n_frames * 8, hipMemcpyHostToDevice));
     RS_HIP(hipMemsetAsync(c->rect_count.p, 0, (size_t)n_frames * 16, c->stream));
     if (stab_fill_targets(c, cfg, targets, n_frames) || stab_rays(c, cfg)) return 1;
@@ -4900,65 +4791,28 @@ int rship_infill_frames(rship_ctx* c, const uint8_t* frames, uint32_t n_frames, 
     A.fill = S.fill;
     A.n_frames = n_frames;
     A.radius = radius;
-    // the first and one past the last input frame of the chunk f0 .. f0 + cnt - 1
-    auto first_in = [&](uint32_t f0) { return f0 > r ? f0 - r : 0u; };
-    auto end_in = [&](uint32_t f0, uint32_t cnt) { return (uint32_t)std::min<uint64_t>(n_frames, (uint64_t)f0 + cnt + r); };
-    auto upload = [&](int slot, bool reused, uint32_t f0, uint32_t cnt) -> int {
-        if (reused) RS_HIP(hipStreamWaitEvent(c->copy_stream, c->trk_k[slot], 0));
-        const uint32_t lo = first_in(f0);
-        if (!dev_in && rect_copy(c, (uint8_t*)c->rect_slot[slot].p + tab_bytes, w, px_in, frames + (size_t)lo * frame_stride, pitch, frame_stride, w, h,
-                                 end_in(f0, cnt) - lo))
-            return 1;
-        RS_HIP(hipEventRecord(c->trk_up[slot], c->copy_stream));
-        return 0;
-    };
-    const dim3 grid((ow + kRectTW - 1) / kRectTW, (oh + kRectTH - 1) / kRectTH, 1);
-    bool used[2] = {false, false};
-    int slot = 0;
-    if (upload(0, false, 0, std::min(chunk, n_frames))) return 1;
-    for (uint32_t f0 = 0; f0 < n_frames;) {
-        const uint32_t cnt = std::min(chunk, n_frames - f0);
-        uint8_t* base = (uint8_t*)c->rect_slot[slot].p;
-        uint8_t* s_in = base + tab_bytes;
-        uint8_t* s_out = s_in + (dev_in ? 0 : (size_t)held * px_in);
-        RS_HIP(hipStreamWaitEvent(c->stream, c->trk_up[slot], 0));
-        R.rows_tab = (float*)base;
-        R.f0 = f0;
-        hipLaunchKernelGGL(infill_rows_kernel, dim3((h + 1 + 255) / 256, places, cnt), dim3(256), 0, c->stream, R);
-        RS_HIP(hipGetLastError());
-        A.rows_tab = (const float*)base;
-        A.outside = (unsigned long long*)c->rect_count.p + f0;
-        A.borrowed = (unsigned long long*)c->rect_count.p + n_frames + f0;
-        A.f0 = f0;
-        if (dev_in) { A.src = frames; A.src0 = 0; A.src_pitch = pitch; A.src_stride = frame_stride; }
-        else { A.src = s_in; A.src0 = first_in(f0); A.src_pitch = w; A.src_stride = px_in; }
-        if (dev_out) { A.dst = out + (size_t)f0 * out_stride; A.dst_pitch = out_pitch; A.dst_stride = out_stride; }
-        else { A.dst = s_out; A.dst_pitch = ow; A.dst_stride = px_out; }
-        const dim3 g(grid.x, grid.y, cnt);
-        if (cfg->camera == 0 && cfg->filter == 0) hipLaunchKernelGGL((infill_kernel<0, 0>), g, dim3(256), 0, c->stream, A);
-        else if (cfg->camera == 0) hipLaunchKernelGGL((infill_kernel<0, 1>), g, dim3(256), 0, c->stream, A);
-        else if (cfg->filter == 0) hipLaunchKernelGGL((infill_kernel<1, 0>), g, dim3(256), 0, c->stream, A);
-        else hipLaunchKernelGGL((infill_kernel<1, 1>), g, dim3(256), 0, c->stream, A);
-        RS_HIP(hipGetLastError());
-        RS_HIP(hipEventRecord(c->trk_k[slot], c->stream));
-        used[slot] = true;
-        const uint32_t next = f0 + cnt;
-        if (next < n_frames && upload(slot ^ 1, used[slot ^ 1], next, std::min(chunk, n_frames - next))) return 1;
-        if (!dev_out) {
-            RS_HIP(hipStreamWaitEvent(c->copy_stream, c->trk_k[slot], 0));
-            if (rect_copy(c, out + (size_t)f0 * out_stride, out_pitch, out_stride, s_out, ow, px_out, ow, oh, cnt)) return 1;
-        }
-        f0 = next;
-        slot ^= 1;
-    }
     // both counts in one download
-    std::vector<uint64_t> counts;
-    if (n_outside || n_borrowed) {
-        counts.resize((size_t)n_frames * 2);
-        RS_HIP(hipMemcpyAsync(counts.data(), c->rect_count.p, (size_t)n_frames * 16, hipMemcpyDeviceToHost, c->stream));
-    }
-    RS_HIP(hipStreamSynchronize(c->copy_stream));
-    if (sync_stream(c)) return 1;
+    std::vector<uint64_t> counts(n_outside || n_borrowed ? 2 * (size_t)n_frames : 0);
+    if (frame_pipeline(c, P, 1, gray_image(frames, pitch, frame_stride), gray_image(out, out_pitch, out_stride), counts.empty() ? nullptr : counts.data(),
+                       counts.size(), [&](const FrameChunk& K) -> int {
+            R.rows_tab = (float*)K.base;
+            R.f0 = K.f0;
+            hipLaunchKernelGGL(infill_rows_kernel, dim3((h + 1 + 255) / 256, places, K.cnt), dim3(256), 0, c->stream, R);
+            RS_HIP(hipGetLastError());
+            A.rows_tab = (const float*)K.base;
+            A.outside = (unsigned long long*)c->rect_count.p + K.f0;
+            A.borrowed = (unsigned long long*)c->rect_count.p + n_frames + K.f0;
+            A.f0 = K.f0;
+            // (device frames: the kernel reads the neighbours in place, from frame 0 of the call)
+            A.src = dev_in ? frames : K.src[0];
+            A.src0 = dev_in ? 0 : K.src0;
+            A.src_pitch = K.src_pitch[0]; A.src_stride = K.src_stride[0];
+            A.dst = K.dst[0]; A.dst_pitch = K.dst_pitch[0]; A.dst_stride = K.dst_stride[0];
+            camfilt_launch<PickInfill>(c, cfg->camera, cfg->filter, stab_grid(cfg, K.cnt), A);
+            RS_HIP(hipGetLastError());
+            return 0;
+        }))
+        return 1;
     if (n_outside) std::copy(counts.begin(), counts.begin() + n_frames, n_outside);
     if (n_borrowed) std::copy(counts.begin() + n_frames, counts.end(), n_borrowed);
     return 0;

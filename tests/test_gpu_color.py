@@ -330,6 +330,35 @@ def test_chunks_pitched_views_and_device_tensors_do_not_change_the_result(scene)
     np.testing.assert_array_equal(got_n, want_n)
 
 
+def test_mixed_memory_kinds_across_chunks(scene, monkeypatch):
+    """NV12 device tensors into host arrays and host arrays into device tensors, each with a budget of one and a half of
+    the frames that then pass through a slot: three chunks through both slots.  Where the output planes lie in a slot
+    depends on whether the input planes pass through it too; the result is the unchunked all-host call's."""
+    from rssync_amd import color, synth
+    p, lens, times = scene["problem"], scene["lens"], scene["times"]
+    col = cr.scene()
+    y, uv = col["y"], col["uv"]
+    orows, ocols = OUT
+    kw = dict(sigma=sr.SIGMA, out_size=(ocols, orows))
+    (one_y, one_uv), one_n = p.stabilize_color(color.NV12, (y, uv), times, lens, synth.D_TRUE, **kw)
+    tabs, px_in, px_out = (rr.ROWS + 1) * 36 + (cr.C_ROWS + 1) * 36, rr.ROWS * rr.COLS * 3 // 2, orows * ocols * 3 // 2
+    dev = (torch.from_numpy(np.array(y)).to("cuda:0"), torch.from_numpy(np.array(uv)).to("cuda:0"))
+    (got_y, got_uv), got_n = color.stabilize_color_budget(p, color.NV12, dev, times, lens, synth.D_TRUE, 2 * 1.5 * (tabs + px_out), **kw)
+    np.testing.assert_array_equal(got_y, one_y)
+    np.testing.assert_array_equal(got_uv, one_uv)
+    np.testing.assert_array_equal(got_n, one_n)
+    # the budget wrapper writes host arrays: hand the launcher device tensors in their place
+    lib = color.library()
+    launcher = lib.rship_color_frames
+    dout = (torch.zeros(one_y.shape, dtype=torch.uint8, device="cuda:0"), torch.zeros(one_uv.shape, dtype=torch.uint8, device="cuda:0"))
+    dst, _keep = color._image(color.NV12, dout, rr.N_FRAMES, orows, ocols, True)
+    monkeypatch.setattr(lib, "rship_color_frames", lambda *a: launcher(*a[:6], C.byref(dst), *a[7:]))
+    _, got_n = color.stabilize_color_budget(p, color.NV12, (y, uv), times, lens, synth.D_TRUE, 2 * 1.5 * (tabs + px_in), **kw)
+    np.testing.assert_array_equal(dout[0].cpu().numpy(), one_y)
+    np.testing.assert_array_equal(dout[1].cpu().numpy(), one_uv)
+    np.testing.assert_array_equal(got_n, one_n)
+
+
 # 9 ---------------------------------------------------------------------------------------------------------------------
 def test_bad_arguments_return_an_error_and_the_next_call_works(scene):
     import rssync_amd

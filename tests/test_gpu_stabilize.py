@@ -280,6 +280,30 @@ def test_chunk_boundaries_and_another_output_size_do_not_change_the_result(scene
         assert int(one_n[k]) == want_n
 
 
+def test_mixed_memory_kinds_across_chunks(scene, monkeypatch):
+    """device frames into a host array and host frames into a device tensor, each with a budget of one and a half of the
+    frames that then pass through a slot: three chunks through both slots.  Where the output lies in a slot depends on
+    whether the input passes through it too; the result is the unchunked all-host call's."""
+    from rssync_amd import stabilize, synth
+    p, frames, times, lens = scene["problem"], scene["frames"], scene["times"], scene["lens"]
+    orows, ocols = 200, 320
+    kw = dict(out_size=(ocols, orows), sigma=sr.SIGMA, fill=5)
+    one, one_n = p.stabilize_frames(frames, times, lens, synth.D_TRUE, **kw)
+    tab, px_in, px_out = (rr.ROWS + 1) * 36, rr.ROWS * rr.COLS, orows * ocols
+    dev = torch.from_numpy(np.array(frames)).to("cuda:0")
+    got, got_n = stabilize.stabilize_frames_budget(p, dev, times, lens, synth.D_TRUE, 2 * 1.5 * (tab + px_out), **kw)
+    np.testing.assert_array_equal(got, one)
+    np.testing.assert_array_equal(got_n, one_n)
+    # the budget wrapper writes a host array: hand the launcher a device tensor in its place
+    lib = stabilize.library()
+    launcher = lib.rship_stabilize_frames
+    dout = torch.zeros((rr.N_FRAMES, orows, ocols), dtype=torch.uint8, device="cuda:0")
+    monkeypatch.setattr(lib, "rship_stabilize_frames", lambda *a: launcher(*a[:8], dout.data_ptr(), *a[9:]))
+    _, got_n = stabilize.stabilize_frames_budget(p, frames, times, lens, synth.D_TRUE, 2 * 1.5 * (tab + px_in), **kw)
+    np.testing.assert_array_equal(dout.cpu().numpy(), one)
+    np.testing.assert_array_equal(got_n, one_n)
+
+
 # 8 ---------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("sigma", [0.1, 0.2])
 def test_coverage_and_the_chosen_zoom(scene, sigma):
