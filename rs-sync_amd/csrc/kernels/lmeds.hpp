@@ -10,7 +10,7 @@ namespace {
 #define RSSYNC_K2_COUNTERS 0
 #endif
 #if RSSYNC_K2_COUNTERS
-__device__ unsigned long long g_k2_counters[16];
+__device__ unsigned long long g_k2_counters[18];
 #define K2_COUNT(i) do { if ((threadIdx.x & 63) == 0) atomicAdd(&g_k2_counters[i], 1ull); } while (0)
 #else
 #define K2_COUNT(i) do { } while (0)
@@ -33,6 +33,8 @@ __device__ unsigned long long g_k2_counters[16];
 // 6 candidates redone without the provisional bound   7 sweeps that started without any bound (wave max)
 // 8 contenders swept again and closed exactly (lazy selection: overlapping brackets)
 // 9 sweeps that needed their last group of rows (early rejection did not apply)
+// 16 narrowings abandoned (eager bound: the bracket's lower end reached another hypothesis's published bound)
+// 17 bounds published before the narrowing ended (eager bound: a counting pass lowered the bracket's upper end)
 
 // ---------------------------------------------------------------------------
 // K2: LMedS tile kernel
@@ -281,16 +283,40 @@ __device__ __forceinline__ uint32_t uniform_u32(uint32_t v) { return (uint32_t)_
 //   * or, if stop_elems > 0, as soon as hi < hi_limit and the bracket holds at most stop_elems elements: the
 //     caller only needs to know the element that closely (lazy selection, below).
 // All bookkeeping is wave-uniform and kept on the scalar unit; only the secant formula itself runs on the VALU.
+//
+// THE EAGER BOUND (round 8; EAGER, `key` = the workgroup's packed bound in LDS, lazy selection below).  The waves of a
+// workgroup narrow different hypotheses at the same time, and exactly one of them can win.  So a narrowing
+//   * PUBLISHES every upper end a pass lowers, at once: count(|r| < hi) > kq, so this hypothesis's quartile lies below hi
+//     and hi is an exclusive upper bound of the best quartile -- the invariant the publish after the narrowing relies on;
+//   * ABANDONS (returns false) as soon as its lower end has reached the bound: the best quartile is < bound <= lo <= this
+//     hypothesis's quartile, strictly worse, so no tie is involved and no record is needed.  The hypothesis that holds the
+//     smallest published hi has lo < hi and never abandons.
+// The bound is read once per pass, never waited for.
+#ifndef RSSYNC_K2_EAGER_BOUND   // (0: round 7's protocol -- the bound read before the sweep, published when the narrowing has ended -- for the A/B of profiles/r8_k2_eager_bound_ab.txt)
+#define RSSYNC_K2_EAGER_BOUND 1
+#endif
 struct Bracket {
     uint32_t lo, c_lo, hi, c_hi;
 };
-template <int NR, int G = 1> // G: wave_count_lt's grouping
-__device__ __forceinline__ void narrow_kth(const uint32_t (&r)[NR], uint32_t kq, Bracket& b, uint32_t stop_elems, uint32_t hi_limit) {
+// the bound's high word (little endian: the second dword of the packed key), uniform
+__device__ __forceinline__ uint32_t key_bound(const unsigned long long* key) {
+    return uniform_u32(__hip_atomic_load(reinterpret_cast<const uint32_t*>(key) + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+}
+template <int NR, int G = 1, bool EAGER = false> // G: wave_count_lt's grouping
+__device__ __forceinline__ bool narrow_kth(const uint32_t (&r)[NR], uint32_t kq, Bracket& b, uint32_t stop_elems, uint32_t hi_limit,
+                                           unsigned long long* key = nullptr) {
     uint32_t lo = b.lo, c_lo = b.c_lo, hi = b.hi, c_hi = b.c_hi;
     uint32_t a1 = lo, c1 = c_lo, a2 = hi, c2 = c_hi; // the two most recent (pivot, count) points
+    bool alive = true;
     for (int it = 0;; ++it) {
         if (hi - lo == 1u) break;
         if (stop_elems && hi < hi_limit && c_hi - c_lo <= stop_elems) break;
+        if constexpr (EAGER) {
+            // (measured beside it and not kept: a pivot AT the bound whenever the bound lies below the secant's pivot -- 9.9
+            // passes per pair instead of 10.9, but the benchmark's instantiation spilled 20 registers and ran 0.25 ms per
+            // launch slower than this form: profiles/r8_k2_eager_bound_ab.txt)
+            if (lo >= key_bound(key)) { K2_COUNT(16); alive = false; break; }
+        }
         if (c_hi - c_lo == 1u) {
             K2_COUNT(5);
             // the single element in [lo, hi): smallest |x| >= lo; |x| < lo wraps to a huge difference
@@ -325,9 +351,16 @@ __device__ __forceinline__ void narrow_kth(const uint32_t (&r)[NR], uint32_t kq,
         a1 = a2; c1 = c2;
         a2 = piv; c2 = c;
         if (c <= kq) { lo = piv; c_lo = c; }
-        else { hi = piv; c_hi = c; }
+        else {
+            hi = piv; c_hi = c;
+            if constexpr (EAGER) {
+                K2_COUNT(17);
+                if ((threadIdx.x & 63) == 0) atomicMin(key, (unsigned long long)hi << 32);
+            }
+        }
     }
     b.lo = lo; b.c_lo = c_lo; b.hi = hi; b.c_hi = c_hi;
+    return alive;
 }
 // the exact kq-th smallest, given an exclusive upper bound hi with count(|r| < hi) = c_hi > kq
 template <int NR, int G = 1>
@@ -603,6 +636,10 @@ __global__ __launch_bounds__(BLOCK, BLOCK == 512 ? 2 : (R64 ? 1 : (RPT >= 16 ? (
     constexpr int NR = ROWS / 64; // residual registers per lane: a wave spans the whole tile
     // grouped counting (wave_count_lt) where it costs no spill: the benchmark's shape with the compiled-in window
     constexpr int CG = (MODE == 0 && RPT == 8 && BLOCK == 256 && CAPW != 0 && !R64) ? 4 : 1;
+    // the eager bound (narrow_kth), like CG where it costs no spill: the four-wave fp32 shapes of up to 18 rows per thread and
+    // GuessMotion's search.  The shapes that spill as it is -- 19 .. 24 rows per thread in MODE 0, eight waves -- and the
+    // fp64-rows form keep round 7's protocol: there the new reads moved a few more dwords to scratch.
+    constexpr bool EAGER = RSSYNC_K2_EAGER_BOUND != 0 && LAZY && !R64 && BLOCK == 256 && (RPT <= 18 || MODE == 1);
     __shared__ __attribute__((aligned(16))) float s_n[3][ROWS];
     f4* s_win;
     if constexpr (CAPW != 0) {
@@ -860,10 +897,24 @@ __global__ __launch_bounds__(BLOCK, BLOCK == 512 ? 2 : (R64 ? 1 : (RPT >= 16 ? (
                     uint32_t r2[NR];
                     // quartile_h < T  <=>  more than kq |residuals| lie below T.  A hypothesis whose quartile EQUALS the
                     // best one passes as well (T is exclusive and above it): ties are settled among the contenders.
-                    // (T is read before the sweep: a bound that has tightened meanwhile only makes this test milder.)
-                    const uint32_t T = (uint32_t)(__hip_atomic_load(&s_key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >> 32);
+                    // (Any T that was the bound at some time will do: one that has tightened since only makes this test milder.
+                    // The eager bound reads it AFTER the sweep -- what the other waves published meanwhile counts -- and
+                    // issues the read ahead of the last rows it sweeps first, whose LDS reads cover its latency.)
+                    uint32_t T;
+                    if constexpr (!EAGER) T = (uint32_t)(__hip_atomic_load(&s_key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >> 32);
                     uint32_t tot;
-                    if (NR >= 16) {
+                    if (NR >= 16 && EAGER) {
+                        constexpr int GL = NR / 4 - 1;
+                        sweep_tile<NR, 0, GL - 1>(p4x, p4y, p4z, lane, f3{hv.x, hv.y, hv.z}, r2);
+                        const uint32_t t_new = __hip_atomic_load(reinterpret_cast<const uint32_t*>(&s_key) + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        sweep_tile<NR, GL - 1, GL>(p4x, p4y, p4z, lane, f3{hv.x, hv.y, hv.z}, r2);
+                        T = uniform_u32(t_new); // (one T for the early rejection and for the second count)
+                        tot = wave_count_lt<NR, 0, 4 * GL, CG>(r2, T);
+                        if (tot + 256u <= kq) continue;
+                        K2_COUNT(9);
+                        sweep_tile<NR, GL, GL + 1>(p4x, p4y, p4z, lane, f3{hv.x, hv.y, hv.z}, r2);
+                        tot += wave_count_lt<NR, 4 * GL, NR, CG>(r2, T);
+                    } else if (NR >= 16) {
                         // Four of five hypotheses only have to be turned away, and most of those have a few per cent of
                         // their residuals below T: once all rows but the last 256 are counted and even 256 more could
                         // not lift the count above kq, the last group of rows is neither read nor multiplied.
@@ -876,6 +927,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK == 512 ? 2 : (R64 ? 1 : (RPT >= 16 ? (
                         tot += wave_count_lt<NR, 4 * GL, NR, CG>(r2, T);
                     } else {
                         sweep_tile(p4x, p4y, p4z, lane, f3{hv.x, hv.y, hv.z}, r2);
+                        if constexpr (EAGER) T = key_bound(&s_key);
                         tot = wave_count_lt<NR, 0, NR, CG>(r2, T);
                     }
                     if (tot > kq) {
@@ -889,7 +941,10 @@ __global__ __launch_bounds__(BLOCK, BLOCK == 512 ? 2 : (R64 ? 1 : (RPT >= 16 ? (
                             mx = wave_max_f32(mx);
                             if (finite_f(mx)) b.hi = __float_as_uint(mx) + 1u; // count(|r| < hi) is still tot
                         }
-                        narrow_kth<NR, CG>(r2, kq, b, kLazyElems, T); // until it ends below T and holds <= kLazyElems elements (or is closed)
+                        // until it ends below T and holds <= kLazyElems elements (or is closed) -- or, eager bound, has lost for certain:
+                        // then no record is written.  (The exact closings below -- a hypothesis without room for a record, the
+                        // re-sweep of overlapping contenders -- never abandon: they run to the end as before.)
+                        if (!narrow_kth<NR, CG, EAGER>(r2, kq, b, kLazyElems, T, &s_key)) continue;
                         uint32_t slot = 0;
                         if (lane == 0) {
                             atomicMin(&s_key, (unsigned long long)b.hi << 32);

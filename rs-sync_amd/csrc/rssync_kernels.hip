@@ -3293,14 +3293,14 @@ int rship_debug_init_h(rship_ctx* c, int32_t* get, const int32_t* set, uint32_t 
 }
 
 // dynamic trip counts of the LMedS tile kernel (variant builds with -DRSSYNC_K2_COUNTERS=1 only; zeros otherwise)
-int rship_debug_k2_counters(rship_ctx* c, uint64_t out[16], int reset) {
+int rship_debug_k2_counters(rship_ctx* c, uint64_t out[18], int reset) {
     DeviceGuard dev_guard(c);
-    for (int i = 0; i < 16; ++i) out[i] = 0;
+    for (int i = 0; i < 18; ++i) out[i] = 0;
 #if RSSYNC_K2_COUNTERS
     RS_HIP(hipStreamSynchronize(c->stream));
-    RS_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_k2_counters), 16 * sizeof(uint64_t)));
+    RS_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_k2_counters), 18 * sizeof(uint64_t)));
     if (reset) {
-        const uint64_t zero[16] = {};
+        const uint64_t zero[18] = {};
         RS_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_k2_counters), zero, sizeof(zero)));
     }
 #else

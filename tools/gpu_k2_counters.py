@@ -24,7 +24,7 @@ synth.fill(p, gyro, 0, F, N, seed=0x5EED0003)
 p.upload()
 lib = p._lib
 lib.rship_debug_k2_counters.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]
-buf = (C.c_uint64 * 16)()
+buf = (C.c_uint64 * 18)()
 lib.rship_debug_k2_counters(p.device_context(), buf, 1)
 c, d = p.PreSync(0.0, 0, F, 0.0005, 0.2)
 lib.rship_debug_k2_counters(p.device_context(), buf, 1)
@@ -32,8 +32,10 @@ raw = [int(x) for x in buf]
 pairs = raw[0] or 1
 names = ["frame_candidates", "queue_pops", "hypotheses_swept", "exact_selections", "selection_counting_passes",
          "selection_min_endings", "candidates_redone", "sweeps_without_bound", "contenders_closed_exactly", "sweeps_completed"]
-out = {"frames": F, "tracks": N, "presync": [c, d], "raw": dict(zip(names, raw)),
-       "per_frame_candidate": {n: raw[i] / pairs for i, n in enumerate(names)}}
+eager = {"narrowings_abandoned": 16, "bounds_published_early": 17}  # (the eager bound: zeros in a -DRSSYNC_K2_EAGER_BOUND=0 build)
+out = {"frames": F, "tracks": N, "presync": [c, d], "raw": dict(zip(names, raw), **{n: raw[i] for n, i in eager.items()}),
+       "per_frame_candidate": dict({n: raw[i] / pairs for i, n in enumerate(names)}, **{n: raw[i] / pairs for n, i in eager.items()})}
+out["per_frame_candidate"]["contender_records"] = (raw[3] - raw[16]) / pairs
 print(json.dumps(out, indent=1))
 if raw[11]:  # a -DRSSYNC_K2_TIMING=1 build: ticks of every wave waiting at the candidate loop's barriers
     import sys as _s

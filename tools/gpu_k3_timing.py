@@ -21,7 +21,7 @@ p = rssync_amd.SyncProblem(seed=0x5EED, max_outer_iters=20)
 synth.fill(p, gyro, 0, F, N, seed=0x5EED0003)
 lib = p._lib
 lib.rship_debug_k2_counters.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]
-buf = (C.c_uint64 * 16)()
+buf = (C.c_uint64 * 18)()
 d = synth.D_TRUE + 4e-4
 p.init_motion(d, 0, F - 1)
 for step in (0.0, -2e-4, -1e-4, -5e-5, -2e-5):
