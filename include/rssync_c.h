@@ -158,13 +158,18 @@ int rssync_ext_executor_mismatches(rssync_problem* p, uint64_t* count);
  * searches (one per frame and Sync call) that took their rows from the fp64 streams, in place.  All stay 0 on ordinary
  * footage; RSSYNC_NO_FP64_ROWS=1 (read when a problem is created) switches the mechanism off. */
 int rssync_ext_near_static_stats(rssync_problem* p, uint64_t* pairs, uint64_t* sweeps, uint64_t* searches);
-/* TEST-VARIANTS build of the library only (the product returns an error): later PreSync-type sweeps also store the
- * |residual| bit patterns the LMedS selection worked on; _get returns the last sweep's, [candidate][frame of the selection]
- * [hypothesis][cap_rows] as uint32 (0xffffffff: no such row), dims = {candidates, frames, hypotheses, cap_rows} (out NULL:
- * only the dims).  tests/test_gpu_fuzz.py: the winner is the exact arg-min of the lower quartile, first wins
- * (core_private.cpp:48-56) -- asserted without a tolerance. */
+/* TEST-VARIANTS build of the library only (the product returns an error): later PreSync-type sweeps, and later GuessMotion
+ * searches (rssync_ext_init_motion, the Sync-type calls), also store the |residual| bit patterns the LMedS selection worked
+ * on; _get returns those of the last sweep or the last GuessMotion search, whichever came later, [candidate][frame of the
+ * selection][hypothesis][cap_rows] as uint32 (0xffffffff: no such row), dims = {candidates, frames, hypotheses, cap_rows}
+ * (out NULL: only the dims); a search is one candidate of 200 hypotheses, frames of up to 8192 tracks.
+ * tests/test_gpu_fuzz.py, tests/test_gpu_guess_motion.py: the winner is the exact arg-min of the lower quartile, first wins
+ * (core_private.cpp:48-56) -- asserted without a tolerance.
+ * _contenders_get, after such a search: per frame of the selection the contender records the tile kernel's search asked
+ * for (more than 24: its record table overflowed); *n = the frames, filled when cap >= *n (out NULL: only *n). */
 int rssync_ext_debug_residuals(rssync_problem* p, int on, uint32_t cap_rows);
 int rssync_ext_debug_residuals_get(rssync_problem* p, uint32_t* out, size_t n_words, uint32_t dims[4]);
+int rssync_ext_debug_contenders_get(rssync_problem* p, uint32_t* out, size_t cap, size_t* n);
 /* Diagnostics of the bit-exactness tests (tests/test_gpu_bitexact.py).  GuessMotion's 200-hypothesis search runs
  * in fp32 and leaves one winning hypothesis index per slot (window-major, frames ascending); with recording on,
  * the winners of the last Sync / sync_windows / sync_simplified call can be read back, and set_init_override

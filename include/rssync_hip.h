@@ -243,11 +243,16 @@ int rship_presync_batch_begin(rship_ctx* c, uint32_t n, uint32_t n_cand);
 int rship_presync_batch_collect(rship_ctx* c, uint32_t n_cand, double* win_costs, double* chunk_costs, uint32_t* flags);
 /* TEST-VARIANTS build of the library only (tools/k2_build_variant.sh testvariants -DRSSYNC_TEST_VARIANTS=1; the product
  * refuses): later sweeps also store the |residual| bit patterns they worked on, [candidate][slot][hypothesis][cap_rows]
- * (0xffffffff: no such row); _get copies the last sweep's out (dims = {candidates, slots, hypotheses, cap_rows}; out may
- * be NULL to ask for the dims).  The anchor of tests/test_gpu_fuzz.py: the winner must be the exact arg-min of the
- * residuals' lower quartile with the reference's first-wins rule (core_private.cpp:48-56), no tolerance. */
+ * (0xffffffff: no such row), and later GuessMotion searches (rship_init_motion) theirs, [1][slot][200][cap_rows] -- frames
+ * of up to 8192 tracks; the large-frame kernel's search stores nothing.  _get copies out what the last sweep or the last
+ * GuessMotion search stored, whichever came later (dims = {candidates, slots, hypotheses, cap_rows}; out may be NULL to
+ * ask for the dims).  The anchor of tests/test_gpu_fuzz.py and tests/test_gpu_guess_motion.py: the winner must be the
+ * exact arg-min of the residuals' lower quartile with the reference's first-wins rule (core_private.cpp:48-56), no tolerance.
+ * rship_debug_contenders_get, after such a search: out[slot] = the contender records the tile kernel's search of that slot
+ * asked for (more than 24: its record table overflowed); 0 for slots of the other kernel families; n = the slots. */
 int rship_debug_residuals(rship_ctx* c, int on, uint32_t cap_rows);
 int rship_debug_residuals_get(rship_ctx* c, uint32_t* out, uint64_t n_words, uint32_t dims[4]);
+int rship_debug_contenders_get(rship_ctx* c, uint32_t* out, uint32_t n);
 /* out[0] = (frame, candidate) pairs recomputed with fp64 rows so far on this context, out[1] = sweeps that needed it,
  * out[2] = GuessMotion searches (rship_init_motion, the window executor) that took their rows from the fp64 streams */
 int rship_near_static_stats(rship_ctx* c, uint64_t out[3]);

@@ -91,6 +91,13 @@ struct LmedsParams {
     // the reference's first-wins rule (core_private.cpp:48-56; tests/test_gpu_fuzz.py: the anchor under flip_interval)
     uint32_t* dump;
     uint32_t dump_rows;
+#if RSSYNC_TEST_VARIANTS
+    // GuessMotion's search (MODE 1) dumps as well: [0][slot][hypothesis][dump_rows], all n_hyp hypotheses of its batches, and --
+    // tile kernel -- per slot the number of contender records the search asked for (s_ncont of the final pass: above kContCap
+    // the overflow path ran), so that a test can tell that the inputs it aimed at that path reached it
+    // (tests/test_gpu_guess_motion.py)
+    uint32_t* dump_ncont;
+#endif
 };
 
 // fp64 ROWS FOR NEAR-STATIC FRAMES (round 6).  The reference computes the rows of P, their norms and the safe_normalize
@@ -821,6 +828,9 @@ __global__ __launch_bounds__(BLOCK, BLOCK == 512 ? 2 : (R64 ? 1 : (RPT >= 16 ? (
             guess = uniform_u32(__float_as_uint(__uint_as_float(prev_best) * 1.25f));
         uint32_t bT; // the winner's quartile (exact selection) or an upper bound of it (lazy): the next candidate's bound
         int bH;
+#if RSSYNC_TEST_VARIANTS
+        [[maybe_unused]] uint32_t dump_n_cont = 0; // (LmedsParams::dump_ncont: the records the final pass of the lazy selection asked for)
+#endif
         if (!LAZY) {
         unsigned long long best;
         for (;;) {
@@ -967,6 +977,9 @@ __global__ __launch_bounds__(BLOCK, BLOCK == 512 ? 2 : (R64 ? 1 : (RPT >= 16 ? (
             if (tid == 0) K2_COUNT(6);
             __syncthreads();  // everyone has read the counters before they are reset
         }
+#if RSSYNC_TEST_VARIANTS
+        dump_n_cont = n_cont;
+#endif
         // ---- the decision among the contenders (every thread computes the same) ----
         const uint32_t n_rec = n_cont < (uint32_t)kContCap ? n_cont : (uint32_t)kContCap;
         const unsigned long long ovf = s_exact; // only set when records overflowed
@@ -1022,6 +1035,27 @@ __global__ __launch_bounds__(BLOCK, BLOCK == 512 ? 2 : (R64 ? 1 : (RPT >= 16 ? (
         if (!(finite_f(Mv.x) && finite_f(Mv.y) && finite_f(Mv.z))) bad |= RSHIP_BAD_M;
         if (MODE == 1) { // GuessMotion: only the winner's index leaves this kernel (one candidate per workgroup)
             if (tid == 0) p.best_h[sf] = bH;
+#if RSSYNC_TEST_VARIANTS
+            if (p.dump) {
+                // the search's own residuals, as the sweep's dump below: every hypothesis against this thread's own rows of the
+                // tile in sweep_tile's very expression.  s_hyp only holds the last batch, so each direction is regenerated by the
+                // call the search made (as the closing of overlapping contenders and the winner's direction above are); the tile,
+                // s_min2 and the rays are only read from here on
+                if (tid == 0 && p.dump_ncont) p.dump_ncont[sf] = dump_n_cont;
+                for (uint32_t h = 0; h < p.n_hyp; ++h) {
+                    const f3 hv = hypothesis(tile, p.seed, fr.id, stream, h, N, frame_smin2(), row_scale);
+                    uint32_t* out = p.dump + ((size_t)sf * p.n_hyp + h) * p.dump_rows;
+#pragma unroll 1
+                    for (int j = 0; j < RPT; ++j) {
+                        const uint32_t row = j * BLOCK + tid;
+                        if (row < N && row < p.dump_rows) {
+                            const v2f r01 = v2f{tile.nx[row], 0.f} * hv.x + v2f{tile.ny[row], 0.f} * hv.y + v2f{tile.nz[row], 0.f} * hv.z;
+                            out[row] = __float_as_uint(r01.x) & 0x7fffffffu;
+                        }
+                    }
+                }
+            }
+#endif
             continue;
         }
 

@@ -253,7 +253,7 @@ __device__ __forceinline__ void lmeds_small_body(const LmedsParams& p, uint32_t 
                         if (q + 1 < RPT) r2[q + 1] = __float_as_uint(r01.y);
                     }
 #if RSSYNC_TEST_VARIANTS
-                    if (MODE == 0 && p.dump) { // (lmeds.hpp: LmedsParams::dump -- the residuals the selection below works on)
+                    if (p.dump) { // (lmeds.hpp: LmedsParams::dump -- the residuals the selection below works on; GuessMotion's search: candidate 0, every batch)
                         uint32_t* out = p.dump + (((size_t)c * p.n_sel + sf) * p.n_hyp + (batch + j)) * p.dump_rows;
 #pragma unroll
                         for (int q = 0; q < RPT; ++q) {

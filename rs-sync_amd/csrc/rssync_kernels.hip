@@ -267,9 +267,10 @@ struct rship_ctx {
     uint32_t batch_n = 0, batch_next = 0, batch_rows = 0;
     size_t batch_chunk_stride = 0, batch_win_stride = 0; // doubles per slot in chunk_out / win_out
     // TEST-VARIANTS build: the sweep's own residuals (kernels/lmeds.hpp: LmedsParams::dump) of the last rship_presync_enqueue
-    DevBuf dump;
+    // or rship_init_motion; after the latter also the contender records each slot's search asked for (LmedsParams::dump_ncont)
+    DevBuf dump, dump_ncont;
     bool dump_on = false;
-    uint32_t dump_rows = 0, dump_dims[4] = {0, 0, 0, 0};
+    uint32_t dump_rows = 0, dump_dims[4] = {0, 0, 0, 0}, dump_ncont_n = 0;
     // scratch
     DevBuf kd, frame_cost, best_h, costs, part, flags, stats;
     void* pinned = nullptr;
@@ -1150,7 +1151,7 @@ void rship_destroy(rship_ctx* c) {
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
     DevBuf* bufs[] = {&c->pack_list, &c->retime_ro, &c->coef, &c->coef64, &c->raw, &c->rays_a, &c->rays_b, &c->rays64, &c->frames, &c->sel, &c->M, &c->k, &c->grp, &c->grp_off,
                       &c->plan_idx, &c->plan_chunk_off, &c->plan_win_off, &c->chunk_out, &c->win_out, &c->loop_state, &c->kd, &c->kd64, &c->init_h,
-                      &c->frame_cost, &c->best_h, &c->costs, &c->part, &c->flags, &c->stats, &c->redo_mask, &c->redo_delays, &c->redo_count, &c->init_delays64, &c->dump,
+                      &c->frame_cost, &c->best_h, &c->costs, &c->part, &c->flags, &c->stats, &c->redo_mask, &c->redo_delays, &c->redo_count, &c->init_delays64, &c->dump, &c->dump_ncont,
                       &c->big_scratch, &c->mo_scratch, &c->mo_evals, &c->mo_order,
                       &c->g_ts, &c->g_rates, &c->g_us, &c->g_dq, &c->g_q, &c->g_knots, &c->g_cf, &c->g_status,
                       &c->trk_slot[0], &c->trk_slot[1], &c->trk_out, &c->ftr_cells, &c->ftr_out,
@@ -1958,6 +1959,7 @@ int rship_presync_enqueue(rship_ctx* c, const int32_t* kd, const float* fd, cons
         p.src64.coef = nullptr;
         c->pend_redo.armed = false;
         c->dump_dims[0] = n_cand; c->dump_dims[1] = ns; c->dump_dims[2] = n_hyp; c->dump_dims[3] = c->dump_rows;
+        c->dump_ncont_n = 0; // (record counts belong to a GuessMotion search: rship_debug_contenders_get)
     }
     if (launch_lmeds<0>(c, p, step_knots, chunk, &c->last_lmeds_cap, &c->last_lmeds_chunk)) return 1;
     c->pend_redo.p = p;
@@ -2185,6 +2187,22 @@ int rship_init_motion(rship_ctx* c, const int32_t* kd, const float* fd, const in
         p.fd64 = (const double*)((const char*)c->init_delays64.p + pad * 4);
         p.redo_count = (unsigned long long*)c->redo_count.p;
     }
+#if RSSYNC_TEST_VARIANTS
+    if (c->dump_on) { // (rship_debug_residuals, as rship_presync_enqueue arms it) -- the fp32 search's own residuals, [0][slot][hypothesis][row]; no fp64 form of any frame
+        const uint32_t ns = c->n_sel;
+        const uint64_t words = (uint64_t)ns * n_hyp * c->dump_rows;
+        if (words > ((uint64_t)3 << 30) / 4) return set_err(c, "debug_residuals: more than 3 GB of residuals: search fewer frames per call");
+        if (ensure(c, c->dump, (size_t)words * 4) || ensure(c, c->dump_ncont, (size_t)ns * 4)) return 1;
+        RS_HIP(hipMemsetAsync(c->dump.p, 0xff, (size_t)words * 4, c->stream));
+        RS_HIP(hipMemsetAsync(c->dump_ncont.p, 0, (size_t)ns * 4, c->stream));
+        p.dump = (uint32_t*)c->dump.p;
+        p.dump_rows = c->dump_rows;
+        p.dump_ncont = (uint32_t*)c->dump_ncont.p;
+        p.src64.coef = nullptr; // (the fp64-rows watch is off for this launch)
+        c->dump_dims[0] = 1; c->dump_dims[1] = ns; c->dump_dims[2] = n_hyp; c->dump_dims[3] = c->dump_rows;
+        c->dump_ncont_n = ns;
+    }
+#endif
     if (launch_lmeds<1>(c, p, 0.0, 1u, &c->last_init_cap, nullptr)) return 1;
     c->init_pending = true;
     c->init_seed = seed;
@@ -3047,7 +3065,9 @@ int rship_lmeds_shapes(rship_ctx* c, uint32_t out[6]) {
 
 // TEST-VARIANTS build only: every later rship_presync_enqueue also stores the |residual| bit patterns of its sweep --
 // [candidate][slot][hypothesis][cap_rows], 0xffffffff where there is no row -- for rship_debug_residuals_get (after the
-// collect).  The product build has no such code in its kernels and refuses.
+// collect); and every later rship_init_motion those of GuessMotion's search, [1][slot][200][cap_rows] (frames of up to 8192
+// tracks; the large-frame kernel's search stores nothing).  _get returns the last sweep's or the last search's, whichever
+// came later.  The product build has no such code in its kernels and refuses.
 int rship_debug_residuals(rship_ctx* c, int on, uint32_t cap_rows) {
 #if RSSYNC_TEST_VARIANTS
     if (on && !cap_rows) return set_err(c, "debug_residuals: cap_rows must be positive");
@@ -3067,6 +3087,17 @@ int rship_debug_residuals_get(rship_ctx* c, uint32_t* out, uint64_t n_words, uin
     if (!have || n_words < have || !c->dump.p) return set_err(c, "debug_residuals_get: nothing stored, or the buffer is too small");
     RS_HIP(hipStreamSynchronize(c->stream));
     RS_HIP(hipMemcpy(out, c->dump.p, (size_t)have * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+// TEST-VARIANTS build only, after an rship_init_motion with the dump on: out[slot] = the contender records that slot's search
+// asked for in the tile kernel (kernels/lmeds.hpp: s_ncont of the final pass; more than kContCap = 24: the table overflowed and
+// the rest were closed at once); 0 for the slots of the other kernel families.  n = the selection's slots.
+int rship_debug_contenders_get(rship_ctx* c, uint32_t* out, uint32_t n) {
+    DeviceGuard dev_guard(c);
+    if (!c->dump_ncont_n || !c->dump_ncont.p) return set_err(c, "debug_contenders_get: no GuessMotion search has stored its record counts (test-variants build, after rship_debug_residuals)");
+    if (!out || n != c->dump_ncont_n) return set_err(c, "debug_contenders_get: count differs from the selection of the last search");
+    RS_HIP(hipStreamSynchronize(c->stream));
+    RS_HIP(hipMemcpy(out, c->dump_ncont.p, (size_t)n * 4, hipMemcpyDeviceToHost));
     return 0;
 }
 // out[0]: (frame, candidate) pairs of PreSync sweeps recomputed with fp64 rows so far (near-static frames: kernels/lmeds.hpp,

@@ -67,6 +67,10 @@ extern "C" int rship_gyro_rates_condition(rship_ctx* c, int32_t lowpass_divider,
 extern "C" int rship_gyro_conditioned(rship_ctx* c, double* rates, uint32_t cap, uint32_t* n, double* sample_rate, double* first_timestamp)
     __attribute__((weak));
 
+// ... and the record counts of GuessMotion's search (test-variants build: rssync_ext_debug_contenders_get): a device layer
+// without the entry -- a test double written before it existed -- still links, and the call is refused
+extern "C" int rship_debug_contenders_get(rship_ctx* c, uint32_t* out, uint32_t n) __attribute__((weak));
+
 using rssync_host::g_last_error;
 using rssync_host::g_panic_mode;
 using rssync_host::guarded;
@@ -355,6 +359,13 @@ class SyncProblemHip final : public ISyncProblem {
     void debug_residuals_get(uint32_t* out, size_t n_words, uint32_t dims[4]) {
         if (shards_.size() != 1) panic("debug_residuals: one device only");
         hip_check(shards_[0], rship_debug_residuals_get(shards_[0].ctx, out, n_words, dims), "debug_residuals_get");
+    }
+    size_t debug_contenders_get(uint32_t* out, size_t cap) { // -> the slots of the selection; out filled when it holds them
+        if (shards_.size() != 1) panic("debug_residuals: one device only");
+        if (!rship_debug_contenders_get) panic("debug_contenders_get: this device layer does not have it");
+        const size_t n = sel_.size();
+        if (out && cap >= n) hip_check(shards_[0], rship_debug_contenders_get(shards_[0].ctx, out, (uint32_t)n), "debug_contenders_get");
+        return n;
     }
     // (frame, candidate) pairs of PreSync sweeps recomputed with fp64 rows / sweeps that needed it, over this object's devices
     void near_static_stats(uint64_t out[3]) {
@@ -2282,6 +2293,12 @@ int rssync_ext_debug_residuals(rssync_problem* p, int on, uint32_t cap_rows) {
 }
 int rssync_ext_debug_residuals_get(rssync_problem* p, uint32_t* out, size_t n_words, uint32_t dims[4]) {
     return guarded([&] { p->impl->debug_residuals_get(out, n_words, dims); });
+}
+int rssync_ext_debug_contenders_get(rssync_problem* p, uint32_t* out, size_t cap, size_t* n) {
+    return guarded([&] {
+        const size_t have = p->impl->debug_contenders_get(out, cap);
+        if (n) *n = have;
+    });
 }
 
 int rssync_ext_executor_mismatches(rssync_problem* p, uint64_t* count) {

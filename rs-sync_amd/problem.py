@@ -71,6 +71,7 @@ SIGNATURES = {
     "rssync_ext_near_static_stats": (C.c_int, [C.c_void_p, _PU64, _PU64, _PU64]),
     "rssync_ext_debug_residuals": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32]),
     "rssync_ext_debug_residuals_get": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_uint32)]),
+    "rssync_ext_debug_contenders_get": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_size_t)]),
     "rssync_ext_record_init_winners": (C.c_int, [C.c_void_p, C.c_int]),
     "rssync_ext_last_init_winners": (C.c_int, [C.c_void_p, _PI32, C.c_size_t, C.POINTER(C.c_size_t)]),
     "rssync_ext_set_init_override": (C.c_int, [C.c_void_p, _PI32, C.c_size_t]),
@@ -358,16 +359,27 @@ class SyncProblem:
         return dict(runs=runs.value, checked=chk.value, head=q[0], tail=q[1], ring_cells=q[2], waves=q[3], mismatches=mm.value)
 
     def debug_residuals(self, on=True, cap_rows=0):
-        """TEST-VARIANTS build only: later sweeps also store the |residuals| their LMedS selection worked on"""
+        """TEST-VARIANTS build only: later sweeps, and later GuessMotion searches (init_motion, Sync), also store the
+        |residuals| their LMedS selection worked on"""
         self._check(self._lib.rssync_ext_debug_residuals(self._h, 1 if on else 0, int(cap_rows)))
 
     def debug_residuals_get(self):
-        """-> float32 [candidates][frames][hypotheses][cap_rows] of the last sweep (NaN where there is no row)"""
+        """-> float32 [candidates][frames][hypotheses][cap_rows] of the last sweep or the last GuessMotion search (one
+        candidate, 200 hypotheses), whichever came later (NaN where there is no row)"""
         dims = (C.c_uint32 * 4)()
         self._check(self._lib.rssync_ext_debug_residuals_get(self._h, None, 0, dims))
         out = np.zeros(tuple(int(x) for x in dims), dtype=np.uint32)
         self._check(self._lib.rssync_ext_debug_residuals_get(self._h, _p(out, C.POINTER(C.c_uint32)), out.size, dims))
         return out.view(np.float32)
+
+    def debug_contenders_get(self):
+        """TEST-VARIANTS build only, after a GuessMotion search with debug_residuals on -> uint32 [frames]: the contender
+        records the tile kernel's search of each frame asked for (more than 24: its record table overflowed)"""
+        n = C.c_size_t()
+        self._check(self._lib.rssync_ext_debug_contenders_get(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=np.uint32)
+        self._check(self._lib.rssync_ext_debug_contenders_get(self._h, _p(out, C.POINTER(C.c_uint32)), out.size, C.byref(n)))
+        return out
 
     def near_static_stats(self):
         """-> dict(pairs, sweeps): (frame, candidate) pairs of PreSync sweeps recomputed with fp64 rows so far (near-static

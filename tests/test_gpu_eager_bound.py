@@ -8,8 +8,9 @@ a ragged last chunk, clusters of near-equal quartiles, quartiles equal BIT FOR B
 rule with > in place of >=, or an inclusive bound, would drop the earlier hypothesis), the smallest shape with the early
 rejection, 16 rows per thread, and GuessMotion's 200-hypothesis search, whose record table can overflow.
 
-The test-variants build has no exact form of GuessMotion's search (MODE 1): there, three runs of the product are compared
-with each other."""
+GuessMotion's search (MODE 1) has no exact-selection KERNEL to be compared with; its anchor is the dump of its own residuals,
+tests/test_gpu_guess_motion.py: the winner is the exact first-wins arg-min of the lower quartile, table overflow included.
+Here three runs of the product are compared with each other."""
 import os
 
 import numpy as np
@@ -102,9 +103,9 @@ def test_other_shapes(built, variants_lib, F, N, shape, own_shape):
 
 
 def test_guess_motion_search_is_repeatable(built, bench_scene):
-    """Sync's start: GuessMotion's 200 hypotheses per frame in batches of 64 (MODE 1 of the tile kernel).  The test-variants
-    build has no exact-selection form of that mode, so three runs of the product are compared with each other: the same
-    trace bits, the same return."""
+    """Sync's start: GuessMotion's 200 hypotheses per frame in batches of 64 (MODE 1 of the tile kernel).  That each winner
+    is the exact arg-min is tests/test_gpu_guess_motion.py's; here three runs of the product are compared with each other: the
+    same trace bits, the same return."""
     gyro, frames = bench_scene
     F = len(frames)
     runs = []
