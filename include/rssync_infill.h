@@ -36,7 +36,7 @@
  * Errors, besides those of rssync_stabilize.h: a radius outside 0 .. 8.  Each returns non-zero and leaves the problem
  * usable.
  *
- * Not here: colour and 16-bit formats (rssync_color.h, rssync_color16.h); a zoom per frame (rssync_zoom.h); blending or
+ * Not here: colour and 16-bit formats (rssync_colorinfill.h has them); a zoom per frame (rssync_zoom.h); blending or
  * feathering at the seam between a frame and its donor; neighbours that are not frames of the call.
  */
 #ifndef RSSYNC_INFILL_H

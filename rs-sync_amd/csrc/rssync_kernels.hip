@@ -64,6 +64,7 @@
 #include "limit_hip.h"
 #include "colorzoom_hip.h"
 #include "infill_hip.h"
+#include "colorinfill_hip.h"
 #include "device_math.hpp"
 #include "sync_math.hpp"
 #include "lens_math.hpp"
@@ -106,6 +107,7 @@ using rs::f4;
 #include "kernels/limit.hpp"
 #include "kernels/colorzoom.hpp"
 #include "kernels/infill.hpp"
+#include "kernels/colorinfill.hpp"
 
 // ===========================================================================
 // host side of the C-ABI
@@ -4504,6 +4506,60 @@ struct ColorLaunch {
     uint32_t fill16_y, fill16_uv;
 };
 
+// The checks of a colour call's images (n_frames >= 1), and what its chunks carry: *q gets the frames, the budget, both row
+// tables' sizes and every plane that has to pass through the slot; tabs and radius stay the caller's.  -> *np planes,
+// *dev_in: the input is device memory
+int color_layout(rship_ctx* c, const rship_color_image* in, uint32_t n_frames, const rship_color_cfg* cfg, const rship_color_image* out,
+                 size_t budget_bytes, rs::FrameLayout* q, int* n_planes, bool* dev_in) {
+    const rship_stabilize_cfg& L = cfg->luma;
+    const bool wide = color_is_16(cfg->format);
+    const uint32_t h = L.height, hc = color_is_yuv(cfg->format) ? h / 2 : 0;
+    rs::FramePlane *pi = q->in, *po = q->out;
+    const int np = color_planes(cfg->format, L.width, h, pi);
+    color_planes(cfg->format, L.out_width, L.out_height, po);
+    for (int k = 0; k < np; ++k) {
+        if (!in->plane[k] || !out->plane[k]) return set_err(c, "color: null pointer");
+        if (wide && (((uintptr_t)in->plane[k] | (uintptr_t)out->plane[k] | in->pitch[k] | out->pitch[k]) & 1u ||
+                     (n_frames > 1 && ((in->stride[k] | out->stride[k]) & 1u))))
+            return set_err(c, "color: alignment: planes, pitches and strides of 16-bit samples must be multiples of 2");
+        if (in->pitch[k] < pi[k].row_bytes || out->pitch[k] < po[k].row_bytes ||
+            (n_frames > 1 && (in->stride[k] < in->pitch[k] * pi[k].rows || out->stride[k] < out->pitch[k] * po[k].rows)))
+            return set_err(c, "color: pitch or frame stride too small");
+    }
+    bool dev_out = false;
+    if (color_kind(c, in, np, "the frames", dev_in) || color_kind(c, out, np, "the stabilised frames", &dev_out)) return 1;
+    // a frame's bytes: both row tables and every plane that has to pass through the slot
+    q->n_frames = n_frames;
+    q->budget = budget_bytes;
+    q->tab[0] = (size_t)(h + 1) * 9 * sizeof(float);
+    q->tab[1] = hc ? (size_t)(hc + 1) * 9 * sizeof(float) : 0;
+    q->n_in = *dev_in ? 0 : np;
+    q->n_out = dev_out ? 0 : np;
+    *n_planes = np;
+    return 0;
+}
+
+// the colour kernels' arguments of a call, all but the chunk's: the cameras (ray maps: the cached ones), the sizes, the fills
+ColorLaunch color_launch(rship_ctx* c, const rship_color_cfg* cfg, const rship_stabilize_cfg& L) {
+    ColorLaunch K{};
+    K.G = stab_args(c, &L); // GRAY8: the stabiliser's kernel
+    ColorArgs& A = K.A;
+    A.luma = color_cam(&L, (const float4*)c->rect_rays.p);
+    if (color_is_yuv(cfg->format)) A.chroma = color_cam(&cfg->chroma, (const float4*)c->rect_rays_c.p);
+    A.width = L.width;
+    A.height = L.height;
+    A.out_width = L.out_width;
+    A.out_height = L.out_height;
+    A.iterations = L.iterations;
+    A.fill = (uint32_t)cfg->fill[0] | (uint32_t)cfg->fill[1] << 8 | (uint32_t)cfg->fill[2] << 16 | (uint32_t)cfg->fill[3] << 24;
+    // the 16-bit kernels' fills as stored words: P010's values sit in the ten high bits
+    const uint32_t sh16 = cfg->format == 17 ? 6 : 0;
+    K.fill16_y = (uint32_t)cfg->fill[0] << sh16;
+    K.fill16_uv = (uint32_t)cfg->fill[1] << sh16 | (uint32_t)cfg->fill[2] << (16 + sh16);
+    if (color_is_16(cfg->format)) A.fill = 0;
+    return K;
+}
+
 // The frames of rship_color_frames and rship_colorzoom_frames through frame_pipeline.  launch(K, f0, cnt) enqueues the
 // kernel that renders the chunk's cnt frames, the first of which is frame f0 of the call; ray_maps: the cached ray maps of
 // cfg's output cameras are needed.
@@ -4514,32 +4570,13 @@ int color_frames_run(rship_ctx* c, const rship_color_image* in, uint32_t n_frame
     if (!in || !out || !frame_times) return set_err(c, "color: null pointer");
     if (!n_frames) return 0;
     rship_stabilize_cfg L = cfg->luma;
-    const bool wide = color_is_16(cfg->format);
-    if (!wide) L.fill = cfg->fill[0]; // (the 16-bit kernels take their fills as arguments of their own)
+    if (!color_is_16(cfg->format)) L.fill = cfg->fill[0]; // (the 16-bit kernels take their fills as arguments of their own)
     const bool yuv = color_is_yuv(cfg->format);
-    const uint32_t h = L.height, ow = L.out_width, oh = L.out_height, hc = yuv ? h / 2 : 0;
+    const uint32_t h = L.height, hc = yuv ? h / 2 : 0;
     rs::FrameLayout q;
-    rs::FramePlane *pi = q.in, *po = q.out;
-    const int np = color_planes(cfg->format, L.width, h, pi);
-    color_planes(cfg->format, ow, oh, po);
-    for (int k = 0; k < np; ++k) {
-        if (!in->plane[k] || !out->plane[k]) return set_err(c, "color: null pointer");
-        if (wide && (((uintptr_t)in->plane[k] | (uintptr_t)out->plane[k] | in->pitch[k] | out->pitch[k]) & 1u ||
-                     (n_frames > 1 && ((in->stride[k] | out->stride[k]) & 1u))))
-            return set_err(c, "color: alignment: planes, pitches and strides of 16-bit samples must be multiples of 2");
-        if (in->pitch[k] < pi[k].row_bytes || out->pitch[k] < po[k].row_bytes ||
-            (n_frames > 1 && (in->stride[k] < in->pitch[k] * pi[k].rows || out->stride[k] < out->pitch[k] * po[k].rows)))
-            return set_err(c, "color: pitch or frame stride too small");
-    }
-    bool dev_in = false, dev_out = false;
-    if (color_kind(c, in, np, "the frames", &dev_in) || color_kind(c, out, np, "the stabilised frames", &dev_out)) return 1;
-    // a frame's bytes: both row tables and every plane that has to pass through the slot
-    q.n_frames = n_frames;
-    q.budget = budget_bytes;
-    q.tab[0] = (size_t)(h + 1) * 9 * sizeof(float);
-    q.tab[1] = yuv ? (size_t)(hc + 1) * 9 * sizeof(float) : 0;
-    q.n_in = dev_in ? 0 : np;
-    q.n_out = dev_out ? 0 : np;
+    int np = 0;
+    bool dev_in = false;
+    if (color_layout(c, in, n_frames, cfg, out, budget_bytes, &q, &np, &dev_in)) return 1;
     const rs::FramePlan P = rs::plan_frames(q);
     if (ensure(c, c->rect_times, (size_t)n_frames * 16) || ensure(c, c->rect_count, (size_t)n_frames * 16)) return 1;
     // the frames' times, then the chroma planes'; the filled pixels of plane 0, then the filled chroma samples
@@ -4560,23 +4597,9 @@ int color_frames_run(rship_ctx* c, const rship_color_image* in, uint32_t n_frame
     R.n_knots = c->n_knots;
     R.rows = h;
     R.rows_c = hc;
-    ColorLaunch K{};
+    ColorLaunch K = color_launch(c, cfg, L);
     StabArgs& G = K.G;
-    G = stab_args(c, &L); // GRAY8: the stabiliser's kernel
     ColorArgs& A = K.A;
-    A.luma = color_cam(&L, (const float4*)c->rect_rays.p);
-    if (yuv) A.chroma = color_cam(&cfg->chroma, (const float4*)c->rect_rays_c.p);
-    A.width = L.width;
-    A.height = h;
-    A.out_width = ow;
-    A.out_height = oh;
-    A.iterations = L.iterations;
-    A.fill = (uint32_t)cfg->fill[0] | (uint32_t)cfg->fill[1] << 8 | (uint32_t)cfg->fill[2] << 16 | (uint32_t)cfg->fill[3] << 24;
-    // the 16-bit kernels' fills as stored words: P010's values sit in the ten high bits
-    const uint32_t sh16 = cfg->format == 17 ? 6 : 0;
-    K.fill16_y = (uint32_t)cfg->fill[0] << sh16;
-    K.fill16_uv = (uint32_t)cfg->fill[1] << sh16 | (uint32_t)cfg->fill[2] << (16 + sh16);
-    if (wide) A.fill = 0;
     // the filled pixels of plane 0 and the filled chroma samples come back as two runs and go to the caller in pairs
     std::vector<uint64_t> counts(n_outside ? 2 * (size_t)n_frames : 0);
     if (frame_pipeline(c, P, np, *in, *out, n_outside ? counts.data() : nullptr, counts.size(), [&](const FrameChunk& C) -> int {
@@ -4846,6 +4869,135 @@ int rship_infill_frames(rship_ctx* c, const uint8_t* frames, uint32_t n_frames, 
         return 1;
     if (n_outside) std::copy(counts.begin(), counts.begin() + n_frames, n_outside);
     if (n_borrowed) std::copy(counts.begin() + n_frames, counts.end(), n_borrowed);
+    return 0;
+}
+
+} // extern "C"
+
+// ===========================================================================
+// colour infill (kernels/colorinfill.hpp; declared in colorinfill_hip.h, called by colorinfill_api.cpp).  The colour
+// front's checks, planes and cameras (color_layout, color_launch) in the infill's pipeline: 2 radius + 1 tables per frame
+// and region, and a halo of `radius` input frames on each side of a chunk, per plane.
+
+namespace {
+template <int C, int F> struct DonorNv12 { static constexpr auto kernel = donor_yuv8_kernel<C, true, F>; };
+template <int C, int F> struct DonorI420 { static constexpr auto kernel = donor_yuv8_kernel<C, false, F>; };
+template <int C, int F> struct DonorRgba { static constexpr auto kernel = donor_rgba8_kernel<C, F>; };
+template <int C, int F> struct DonorGray16 { static constexpr auto kernel = donor_gray16_kernel<C, F>; };
+template <int C, int F> struct DonorP010 { static constexpr auto kernel = donor_yuv16_kernel<C, true, 6, F>; };
+template <int C, int F> struct DonorP016 { static constexpr auto kernel = donor_yuv16_kernel<C, true, 0, F>; };
+template <int C, int F> struct DonorI010 { static constexpr auto kernel = donor_yuv16_kernel<C, false, 0, F>; };
+} // namespace
+
+extern "C" {
+
+int rship_colorinfill_frames(rship_ctx* c, const rship_color_image* in, uint32_t n_frames, const double* frame_times, const double* targets,
+                             const rship_color_cfg* cfg, const rship_color_image* out, uint64_t* n_outside, int32_t radius,
+                             uint64_t* n_borrowed, size_t budget_bytes) {
+    DeviceGuard dev_guard(c);
+    if (color_check(c, cfg)) return 1;
+    if (radius < 0 || radius > rs::kInfillMaxRadius) return set_err(c, "colorinfill: radius must be 0 .. 8");
+    if (!in || !out || !frame_times) return set_err(c, "color: null pointer");
+    if (!n_frames) return 0;
+    rship_stabilize_cfg L = cfg->luma;
+    if (!color_is_16(cfg->format)) L.fill = cfg->fill[0];
+    if (cfg->format == 0) {
+        // GRAY8: the gray infill's kernels; its counts go to the caller in pairs, the chroma entries 0
+        if (!in->plane[0] || !out->plane[0]) return set_err(c, "color: null pointer");
+        std::vector<uint64_t> filled(n_frames), lent(n_frames);
+        if (rship_infill_frames(c, in->plane[0], n_frames, in->pitch[0], in->stride[0], frame_times, targets, &L, out->plane[0], out->pitch[0],
+                                out->stride[0], filled.data(), radius, lent.data(), budget_bytes))
+            return 1;
+        for (uint32_t k = 0; k < n_frames; ++k) {
+            if (n_outside) { n_outside[2 * k] = filled[k]; n_outside[2 * k + 1] = 0; }
+            if (n_borrowed) { n_borrowed[2 * k] = lent[k]; n_borrowed[2 * k + 1] = 0; }
+        }
+        return 0;
+    }
+    const bool yuv = color_is_yuv(cfg->format);
+    const uint32_t h = L.height, hc = yuv ? h / 2 : 0, ow = L.out_width, oh = L.out_height, places = 2 * (uint32_t)radius + 1;
+    rs::FrameLayout q;
+    int np = 0;
+    bool dev_in = false;
+    if (color_layout(c, in, n_frames, cfg, out, budget_bytes, &q, &np, &dev_in)) return 1;
+    // the chunk: per output frame its tables of both regions, its input and its output planes; per slot the halo's input
+    // frames besides
+    q.tabs = places;
+    q.radius = (uint32_t)radius;
+    const rs::FramePlan P = rs::plan_frames(q);
+    // the frames' times, then the chroma planes'; the counts: filled plane 0, filled chroma, borrowed plane 0, borrowed chroma
+    if (ensure(c, c->rect_times, (size_t)n_frames * 16) || ensure(c, c->rect_count, (size_t)n_frames * 32)) return 1;
+    std::vector<double> times(2 * (size_t)n_frames);
+    for (uint32_t k = 0; k < n_frames; ++k) {
+        times[k] = frame_times[k];
+        times[n_frames + k] = frame_times[k] + cfg->chroma_time;
+    }
+    RS_HIP(hipMemcpy(c->rect_times.p, times.data(), times.size() * 8, hipMemcpyHostToDevice));
+    RS_HIP(hipMemsetAsync(c->rect_count.p, 0, (size_t)n_frames * 32, c->stream));
+    if (stab_fill_targets(c, &L, targets, n_frames) || stab_rays(c, &L) || (yuv && stab_rays(c, &cfg->chroma, true))) return 1;
+    DonorRowsArgs R{};
+    R.table = (const double*)c->coef64.p;
+    R.times = (const double*)c->rect_times.p;
+    R.times_c = (const double*)c->rect_times.p + n_frames;
+    R.targets = (const double*)c->stab_targets.p;
+    R.start = L.start;
+    R.fs = L.fs;
+    R.ro = L.lens[0];
+    R.delay = L.delay;
+    R.n_knots = c->n_knots;
+    R.rows = h;
+    R.rows_c = hc;
+    R.n_frames = n_frames;
+    R.radius = radius;
+    const ColorLaunch K = color_launch(c, cfg, L);
+    DonorArgs D{};
+    D.C = K.A;
+    D.fill_y = K.fill16_y;
+    D.fill_uv = K.fill16_uv;
+    D.n_frames = n_frames;
+    D.radius = radius;
+    ColorArgs& A = D.C;
+    unsigned long long* count = (unsigned long long*)c->rect_count.p;
+    // all four counts in one download
+    std::vector<uint64_t> counts(n_outside || n_borrowed ? 4 * (size_t)n_frames : 0);
+    if (frame_pipeline(c, P, np, *in, *out, counts.empty() ? nullptr : counts.data(), counts.size(), [&](const FrameChunk& C) -> int {
+            R.rows_tab = (float*)(C.base + P.off_tab[0]);
+            R.rows_tab_c = (float*)(C.base + P.off_tab[1]);
+            R.f0 = C.f0;
+            hipLaunchKernelGGL(donor_rows_kernel, dim3((h + 1 + (yuv ? hc + 1 : 0) + 255) / 256, places, C.cnt), dim3(256), 0, c->stream, R);
+            RS_HIP(hipGetLastError());
+            A.luma.rows_tab = R.rows_tab;
+            A.chroma.rows_tab = R.rows_tab_c;
+            A.outside = count + C.f0;
+            A.outside_c = count + n_frames + C.f0;
+            D.borrowed = count + 2 * (size_t)n_frames + C.f0;
+            D.borrowed_c = count + 3 * (size_t)n_frames + C.f0;
+            D.f0 = C.f0;
+            // (device frames: the kernels read the neighbours in place, from frame 0 of the call)
+            D.src0 = dev_in ? 0 : C.src0;
+            for (int k = 0; k < np; ++k) {
+                A.src[k] = dev_in ? in->plane[k] : C.src[k]; A.src_pitch[k] = C.src_pitch[k]; A.src_stride[k] = C.src_stride[k];
+                A.dst[k] = C.dst[k]; A.dst_pitch[k] = C.dst_pitch[k]; A.dst_stride[k] = C.dst_stride[k];
+            }
+            const dim3 grid((ow + kRectTW - 1) / kRectTW, (oh + kRectTH - 1) / kRectTH, C.cnt);
+            const dim3 grid_c((ow / 2 + kRectTW - 1) / kRectTW, (oh / 2 + kRectTH - 1) / kRectTH, C.cnt);
+            switch (cfg->format) {
+            case 1: camfilt_launch<DonorNv12>(c, L.camera, L.filter, grid_c, D); break;
+            case 2: camfilt_launch<DonorI420>(c, L.camera, L.filter, grid_c, D); break;
+            case 3: camfilt_launch<DonorRgba>(c, L.camera, L.filter, grid, D); break;
+            case 16: camfilt_launch<DonorGray16>(c, L.camera, L.filter, grid, D); break;
+            case 17: camfilt_launch<DonorP010>(c, L.camera, L.filter, grid_c, D); break;
+            case 18: camfilt_launch<DonorP016>(c, L.camera, L.filter, grid_c, D); break;
+            case 19: camfilt_launch<DonorI010>(c, L.camera, L.filter, grid_c, D); break;
+            }
+            RS_HIP(hipGetLastError());
+            return 0;
+        }))
+        return 1;
+    for (size_t k = 0; k < counts.size() / 4; ++k) {
+        if (n_outside) { n_outside[2 * k] = counts[k]; n_outside[2 * k + 1] = counts[n_frames + k]; }
+        if (n_borrowed) { n_borrowed[2 * k] = counts[2 * (size_t)n_frames + k]; n_borrowed[2 * k + 1] = counts[3 * (size_t)n_frames + k]; }
+    }
     return 0;
 }
 

@@ -767,6 +767,19 @@ class SyncProblem:
         from . import infill
         return infill.stabilize_frames_infilled_budget(self, frames, frame_times, lens, delay, radius, budget_bytes, **params)
 
+    def stabilize_color_infilled(self, fmt, frames, frame_times, lens, delay, radius, **params):
+        """stabilize_color with the borders of every plane taken from up to `radius` neighbouring frames of the call on each
+        side (include/rssync_colorinfill.h, rssync_amd.colorinfill) -> (frames in the layout of `frames`, n_outside (n, 2),
+        n_borrowed (n, 2)).  params: targets, out_size, out, n_borrowed, chroma_site, fills, sigma, zoom, camera, out_camera,
+        iterations, fill, filter."""
+        from . import colorinfill
+        return colorinfill.stabilize_color_infilled(self, fmt, frames, frame_times, lens, delay, radius, **params)
+
+    def stabilize_color_infilled_budget(self, fmt, frames, frame_times, lens, delay, radius, budget_bytes, **params):
+        """stabilize_color_infilled through the internal launcher with a device budget for its chunk slots (tests)."""
+        from . import colorinfill
+        return colorinfill.stabilize_color_infilled_budget(self, fmt, frames, frame_times, lens, delay, radius, budget_bytes, **params)
+
     def stabilize_color(self, fmt, frames, frame_times, lens, delay, **params):
         """Colour frames (rssync_amd.color: GRAY8, NV12, I420, RGBA32, and with uint16 samples GRAY16, P010, P016, I010)
         rendered at the smoothed path's orientations, or at `targets`, all planes of a frame in one pass
