@@ -2,27 +2,26 @@
 // (include/rssync_colorinfill.h): every format of the colour front but GRAY8, which runs kernels/infill.hpp.  Part of the
 // single HIP translation unit rssync_kernels.hip, after kernels/infill.hpp.  A plane is a camera: every plane runs the gray
 // infill's procedure -- the candidate order of infill_math.hpp, a row table per candidate, the first candidate that is inside
-// -- with the plane's camera of kernels/color.hpp, and the value comes from the colour front's samplers, called here through
-// the same device functions in the same order: the bytes are theirs.
+// -- with the plane's camera of kernels/color.hpp, and the value comes from the samplers of kernels/colorsample.hpp on the
+// donor's plane: the bytes are the colour front's.  The kernels have bodies of their own, yuv8's and its siblings' shape
+// with a candidate loop where those have one map evaluation (why not the shared bodies: DESIGN.md, "The colour infill").
 //
-//   donor_rows_kernel                     color_rows_kernel with infill_rows_kernel's indirection: the luma and the chroma
+//   donor_rows_kernel                     color_rows_entry with infill_rows_kernel's indirection: the luma and the chroma
 //                                         table of every (chunk frame, candidate place) in one launch.  Table (f, k) of a
 //                                         plane is rs::stab_row_matrix of the plane's time of f's k-th candidate against the
 //                                         target of f; [chunk frame][place][rows + 1][9] per region.
-//   donor_yuv8_kernel<C, NV12, F>         color_yuv_kernel / bicubic_yuv_kernel: one thread per output chroma sample.  The
+//   donor_yuv8_kernel<C, NV12, F>         yuv8<NV12, F>'s shape: one thread per output chroma sample.  The
 //                                         candidate loop for the chroma sample (U and V: one position, one donor), then one
 //                                         loop for each of the 2 x 2 luma pixels.  Each ray is formed once, before its loop.
-//   donor_yuv16_kernel<C, SEMI, SHIFT, F> color16_yuv_kernel / bicubic16_yuv_kernel: P010 <true, 6>, P016 <true, 0>,
-//                                         I010 <false, 0>
-//   donor_rgba8_kernel<C, F>              color_rgba_kernel / bicubic_rgba_kernel: one position and one donor for the four
-//                                         channels
-//   donor_gray16_kernel<C, F>             color16_gray_kernel / bicubic16_gray_kernel
+//   donor_yuv16_kernel<C, SEMI, SHIFT, F> yuv16<SEMI, SHIFT, F>'s: P010 <true, 6>, P016 <true, 0>, I010 <false, 0>
+//   donor_rgba8_kernel<C, F>              rgba8<F>'s: one position and one donor for the four channels
+//   donor_gray16_kernel<C, F>             gray16<F>'s
 //
 // The steps of the order, the candidate's frame and its table are the same in every lane (blockIdx.z is the frame): they
 // stay in scalar registers, and only the lanes still looking are active, as in infill_kernel.  A wave whose samples are all
-// inside their own frame at candidate 0 runs every loop body once: the colour front's work.  The sampler runs once per
+// inside their own frame at candidate 0 runs every loop body once: the constant camera's work.  The sampler runs once per
 // sample after its loop, on the donor's plane.  Stores are the colour front's.  Four counters per frame -- filled and
-// borrowed, plane 0 and chroma -- by ballots of a wave, one atomic per counter and wave that has any.
+// borrowed, plane 0 and chroma -- through color_count4 / color_count1.
 // (a family name and an argument struct of their own, and an integer FILTER: the tests count the kernels of the other
 // families by substrings of their names)
 #pragma once
@@ -43,25 +42,11 @@ struct DonorRowsArgs {
 };
 
 __global__ __launch_bounds__(256) void donor_rows_kernel(DonorRowsArgs A) {
-    uint32_t j = blockIdx.x * 256 + threadIdx.x;
     const uint32_t k = blockIdx.y, fl = blockIdx.z;
-    const bool chroma = j > A.rows;
-    if (chroma) {
-        j -= A.rows + 1;
-        if (!A.rows_c || j > A.rows_c) return;
-    }
     const int64_t f = (int64_t)A.f0 + fl;
     const int64_t g = rs::infill_candidate(f, (int64_t)A.n_frames, A.radius, (int)k);
     if (g < 0) return;
-    const uint32_t rows = chroma ? A.rows_c : A.rows;
-    const double time = chroma ? A.times_c[g] : A.times[g];
-    const double* t = A.targets + (size_t)f * 4;
-    float m[9];
-    rs::stab_row_matrix(A.table, (int)A.n_knots, A.start, A.fs, A.ro, time, (double)rows, A.delay, rs::RectQuat{t[0], t[1], t[2], t[3]},
-                        (double)j, m);
-    float* out = (chroma ? A.rows_tab_c : A.rows_tab) + (((size_t)fl * (2 * A.radius + 1) + k) * (rows + 1) + j) * 9;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) out[i] = m[i];
+    color_rows_entry(A, blockIdx.x * 256 + threadIdx.x, (size_t)g, (size_t)f, (size_t)fl * (2 * A.radius + 1) + k);
 }
 
 struct DonorArgs {
@@ -106,144 +91,6 @@ __device__ __forceinline__ const uint8_t* donor_plane(const DonorArgs& P, int k,
     return P.C.src[k] + (size_t)(g - (int64_t)P.src0) * P.C.src_stride[k];
 }
 
-// ---- the colour front's samplers at an inside position of the donor's planes ----
-
-template <int FILTER>
-__device__ __forceinline__ uint32_t donor_luma8(const uint8_t* src, uint64_t pitch, int w, int h, float x, float y) {
-    if (FILTER == 0) return rs::rect_sample(src, (size_t)pitch, w, h, x, y);
-    return cubic8_sample(src, pitch, rs::cubic_taps(w, h, x, y));
-}
-
-// U and V of an 8-bit chroma plane pair: pu the interleaved plane (NV12) or U's, pv V's
-template <bool NV12, int FILTER>
-__device__ __forceinline__ void donor_uv8(const uint8_t* pu, uint64_t pitch_u, const uint8_t* pv, uint64_t pitch_v, int cw, int ch, float x,
-                                          float y, uint32_t* cb, uint32_t* cr) {
-    if (FILTER == 0) {
-        const rs::ColorTaps t = rs::color_taps(cw, ch, x, y);
-        if (NV12) {
-            const uint8_t* p = pu + (size_t)t.y0 * pitch_u + 2 * (size_t)t.x0;
-            const uint32_t p00 = color_load16(p), p01 = color_load16(p + 2);
-            const uint32_t p10 = color_load16(p + pitch_u), p11 = color_load16(p + pitch_u + 2);
-            *cb = rs::color_blend((float)(p00 & 255u), (float)(p01 & 255u), (float)(p10 & 255u), (float)(p11 & 255u), t.fx, t.fy);
-            *cr = rs::color_blend((float)(p00 >> 8), (float)(p01 >> 8), (float)(p10 >> 8), (float)(p11 >> 8), t.fx, t.fy);
-        } else {
-            const uint8_t* p = pu + (size_t)t.y0 * pitch_u + t.x0;
-            const uint8_t* q = pv + (size_t)t.y0 * pitch_v + t.x0;
-            *cb = rs::color_blend((float)p[0], (float)p[1], (float)p[pitch_u], (float)p[pitch_u + 1], t.fx, t.fy);
-            *cr = rs::color_blend((float)q[0], (float)q[1], (float)q[pitch_v], (float)q[pitch_v + 1], t.fx, t.fy);
-        }
-    } else {
-        const rs::CubicTaps t = rs::cubic_taps(cw, ch, x, y);
-        if (NV12) {
-            float a[4], b[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const uint8_t* p = pu + (size_t)t.y[j] * pitch_u;
-                const uint32_t p0 = color_load16(p + 2 * (size_t)t.x[0]), p1 = color_load16(p + 2 * (size_t)t.x[1]);
-                const uint32_t p2 = color_load16(p + 2 * (size_t)t.x[2]), p3 = color_load16(p + 2 * (size_t)t.x[3]);
-                a[j] = rs::cubic_row((float)(p0 & 255u), (float)(p1 & 255u), (float)(p2 & 255u), (float)(p3 & 255u), t.wx);
-                b[j] = rs::cubic_row((float)(p0 >> 8), (float)(p1 >> 8), (float)(p2 >> 8), (float)(p3 >> 8), t.wx);
-            }
-            *cb = rs::cubic_finish(a[0], a[1], a[2], a[3], t.wy, 255.0f);
-            *cr = rs::cubic_finish(b[0], b[1], b[2], b[3], t.wy, 255.0f);
-        } else {
-            *cb = cubic8_sample(pu, pitch_u, t);
-            *cr = cubic8_sample(pv, pitch_v, t);
-        }
-    }
-}
-
-template <int SHIFT, int FILTER>
-__device__ __forceinline__ uint32_t donor_luma16(const uint8_t* src, uint64_t pitch, int w, int h, float x, float y, float vmax) {
-    if (FILTER == 0) return color16_sample<SHIFT>(src, pitch, rs::color_taps(w, h, x, y));
-    return rs::cubic_sample16<SHIFT>(src, (size_t)pitch, rs::cubic_taps(w, h, x, y), vmax);
-}
-
-// U and V of a 16-bit chroma plane pair -> their stored words
-template <bool SEMI, int SHIFT, int FILTER>
-__device__ __forceinline__ void donor_uv16(const uint8_t* pu, uint64_t pitch_u, const uint8_t* pv, uint64_t pitch_v, int cw, int ch, float x,
-                                           float y, float vmax, uint32_t* cb, uint32_t* cr) {
-    if (FILTER == 0) {
-        const rs::ColorTaps t = rs::color_taps(cw, ch, x, y);
-        if (SEMI) {
-            const uint8_t* p = pu + (size_t)t.y0 * pitch_u + 4 * (size_t)t.x0;
-            const uint32_t p00 = color_load32(p), p01 = color_load32(p + 4);
-            const uint32_t p10 = color_load32(p + pitch_u), p11 = color_load32(p + pitch_u + 4);
-            *cb = (uint32_t)rs::color_blend16((float)((p00 & 0xffffu) >> SHIFT), (float)((p01 & 0xffffu) >> SHIFT),
-                                              (float)((p10 & 0xffffu) >> SHIFT), (float)((p11 & 0xffffu) >> SHIFT), t.fx, t.fy)
-                  << SHIFT;
-            *cr = (uint32_t)rs::color_blend16((float)(p00 >> (16 + SHIFT)), (float)(p01 >> (16 + SHIFT)), (float)(p10 >> (16 + SHIFT)),
-                                              (float)(p11 >> (16 + SHIFT)), t.fx, t.fy)
-                  << SHIFT;
-        } else {
-            *cb = color16_sample<SHIFT>(pu, pitch_u, t);
-            *cr = color16_sample<SHIFT>(pv, pitch_v, t);
-        }
-    } else {
-        const rs::CubicTaps t = rs::cubic_taps(cw, ch, x, y);
-        if (SEMI) {
-            cubic16_pairs<SHIFT>(pu, pitch_u, t, vmax, cb, cr);
-        } else {
-            *cb = rs::cubic_sample16<SHIFT>(pu, (size_t)pitch_u, t, vmax);
-            *cr = rs::cubic_sample16<SHIFT>(pv, (size_t)pitch_v, t, vmax);
-        }
-    }
-}
-
-// the four channels of an RGBA32 pixel on one set of weights
-template <int FILTER>
-__device__ __forceinline__ uint32_t donor_rgba8(const uint8_t* plane, uint64_t pitch, int w, int h, float x, float y) {
-    uint32_t px = 0;
-    if (FILTER == 0) {
-        const rs::ColorTaps t = rs::color_taps(w, h, x, y);
-        const uint8_t* p = plane + (size_t)t.y0 * pitch + 4 * (size_t)t.x0;
-        const uint32_t p00 = color_load32(p), p01 = color_load32(p + 4);
-        const uint32_t p10 = color_load32(p + pitch), p11 = color_load32(p + pitch + 4);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int s = 8 * k;
-            px |= (uint32_t)rs::color_blend((float)((p00 >> s) & 255u), (float)((p01 >> s) & 255u), (float)((p10 >> s) & 255u),
-                                            (float)((p11 >> s) & 255u), t.fx, t.fy)
-                  << s;
-        }
-    } else {
-        const rs::CubicTaps t = rs::cubic_taps(w, h, x, y);
-        float r[4][4]; // [channel][row]
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const uint8_t* p = plane + (size_t)t.y[j] * pitch;
-            const uint32_t p0 = color_load32(p + 4 * (size_t)t.x[0]), p1 = color_load32(p + 4 * (size_t)t.x[1]);
-            const uint32_t p2 = color_load32(p + 4 * (size_t)t.x[2]), p3 = color_load32(p + 4 * (size_t)t.x[3]);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int s = 8 * k;
-                r[k][j] = rs::cubic_row((float)((p0 >> s) & 255u), (float)((p1 >> s) & 255u), (float)((p2 >> s) & 255u),
-                                        (float)((p3 >> s) & 255u), t.wx);
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) px |= rs::cubic_finish(r[k][0], r[k][1], r[k][2], r[k][3], t.wy, 255.0f) << (8 * k);
-    }
-    return px;
-}
-
-// the four counters of a 4:2:0 kernel: bit 0 .. 3 of fill_y / lent_y are the thread's 2 x 2 luma pixels
-__device__ __forceinline__ void donor_count(const DonorArgs& P, uint32_t fl, bool fill_c, bool lent_c, uint32_t fill_y, uint32_t lent_y) {
-    const unsigned long long mc = __ballot(fill_c), bc = __ballot(lent_c);
-    uint32_t ny = 0, by = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        ny += (uint32_t)__popcll(__ballot((fill_y >> k) & 1u));
-        by += (uint32_t)__popcll(__ballot((lent_y >> k) & 1u));
-    }
-    if ((threadIdx.x & 63) == 0) {
-        if (ny) atomicAdd(P.C.outside + fl, (unsigned long long)ny);
-        if (mc) atomicAdd(P.C.outside_c + fl, (unsigned long long)__popcll(mc));
-        if (by) atomicAdd(P.borrowed + fl, (unsigned long long)by);
-        if (bc) atomicAdd(P.borrowed_c + fl, (unsigned long long)__popcll(bc));
-    }
-}
-
 template <int CAMERA, bool NV12, int FILTER>
 __global__ __launch_bounds__(256) void donor_yuv8_kernel(DonorArgs P) {
     const ColorArgs& A = P.C;
@@ -260,7 +107,7 @@ __global__ __launch_bounds__(256) void donor_yuv8_kernel(DonorArgs P) {
         int64_t g = donor_find<CAMERA>(P, A.chroma, fl, cw, ch, ocw, cu, cv, &x, &y);
         uint32_t cb = (A.fill >> 8) & 255u, cr = (A.fill >> 16) & 255u;
         if (g >= 0) {
-            donor_uv8<NV12, FILTER>(donor_plane(P, 1, g), A.src_pitch[1], NV12 ? nullptr : donor_plane(P, 2, g), A.src_pitch[2], (int)cw, (int)ch,
+            sample_uv8<NV12, FILTER>(donor_plane(P, 1, g), A.src_pitch[1], NV12 ? nullptr : donor_plane(P, 2, g), A.src_pitch[2], (int)cw, (int)ch,
                                     x, y, &cb, &cr);
             lent_c = g != f;
         } else {
@@ -282,7 +129,7 @@ __global__ __launch_bounds__(256) void donor_yuv8_kernel(DonorArgs P) {
                 g = donor_find<CAMERA>(P, A.luma, fl, A.width, A.height, A.out_width, 2 * cu + dx, 2 * cv + dy, &x, &y);
                 uint32_t val = A.fill & 255u;
                 if (g >= 0) {
-                    val = donor_luma8<FILTER>(donor_plane(P, 0, g), A.src_pitch[0], (int)A.width, (int)A.height, x, y);
+                    val = sample_luma8<FILTER>(donor_plane(P, 0, g), A.src_pitch[0], (int)A.width, (int)A.height, x, y);
                     if (g != f) lent_y |= 1u << (2 * dy + dx);
                 } else {
                     fill_y |= 1u << (2 * dy + dx);
@@ -292,7 +139,7 @@ __global__ __launch_bounds__(256) void donor_yuv8_kernel(DonorArgs P) {
             color_store16(dst + (size_t)dy * A.dst_pitch[0], pair);
         }
     }
-    donor_count(P, fl, fill_c, lent_c, fill_y, lent_y);
+    color_count4(A, P.borrowed, P.borrowed_c, fl, fill_c, lent_c, fill_y, lent_y);
 }
 
 template <int CAMERA, bool SEMI, int SHIFT, int FILTER>
@@ -313,7 +160,7 @@ __global__ __launch_bounds__(256) void donor_yuv16_kernel(DonorArgs P) {
         int64_t g = donor_find<CAMERA>(P, A.chroma, fl, cw, ch, ocw, cu, cv, &x, &y);
         uint32_t cb = P.fill_uv & 0xffffu, cr = P.fill_uv >> 16;
         if (g >= 0) {
-            donor_uv16<SEMI, SHIFT, FILTER>(donor_plane(P, 1, g), A.src_pitch[1], SEMI ? nullptr : donor_plane(P, 2, g), A.src_pitch[2], (int)cw,
+            sample_uv16<SEMI, SHIFT, FILTER>(donor_plane(P, 1, g), A.src_pitch[1], SEMI ? nullptr : donor_plane(P, 2, g), A.src_pitch[2], (int)cw,
                                             (int)ch, x, y, kMax, &cb, &cr);
             lent_c = g != f;
         } else {
@@ -335,7 +182,7 @@ __global__ __launch_bounds__(256) void donor_yuv16_kernel(DonorArgs P) {
                 g = donor_find<CAMERA>(P, A.luma, fl, A.width, A.height, A.out_width, 2 * cu + dx, 2 * cv + dy, &x, &y);
                 uint32_t val = P.fill_y;
                 if (g >= 0) {
-                    val = donor_luma16<SHIFT, FILTER>(donor_plane(P, 0, g), A.src_pitch[0], (int)A.width, (int)A.height, x, y, kMax);
+                    val = sample_luma16<SHIFT, FILTER>(donor_plane(P, 0, g), A.src_pitch[0], (int)A.width, (int)A.height, x, y, kMax);
                     if (g != f) lent_y |= 1u << (2 * dy + dx);
                 } else {
                     fill_y |= 1u << (2 * dy + dx);
@@ -345,7 +192,7 @@ __global__ __launch_bounds__(256) void donor_yuv16_kernel(DonorArgs P) {
             color_store32(dst + (size_t)dy * A.dst_pitch[0], pair);
         }
     }
-    donor_count(P, fl, fill_c, lent_c, fill_y, lent_y);
+    color_count4(A, P.borrowed, P.borrowed_c, fl, fill_c, lent_c, fill_y, lent_y);
 }
 
 template <int CAMERA, int FILTER>
@@ -360,18 +207,14 @@ __global__ __launch_bounds__(256) void donor_rgba8_kernel(DonorArgs P) {
         const int64_t g = donor_find<CAMERA>(P, A.luma, fl, A.width, A.height, A.out_width, u, v, &x, &y);
         uint32_t px = A.fill;
         if (g >= 0) {
-            px = donor_rgba8<FILTER>(donor_plane(P, 0, g), A.src_pitch[0], (int)A.width, (int)A.height, x, y);
+            px = sample_rgba8<FILTER>(donor_plane(P, 0, g), A.src_pitch[0], (int)A.width, (int)A.height, x, y);
             lent = g != (int64_t)P.f0 + fl;
         } else {
             filled = true;
         }
         color_store32(A.dst[0] + (size_t)fl * A.dst_stride[0] + (size_t)v * A.dst_pitch[0] + 4 * (size_t)u, px);
     }
-    const unsigned long long m = __ballot(filled), b = __ballot(lent);
-    if ((threadIdx.x & 63) == 0) {
-        if (m) atomicAdd(A.outside + fl, (unsigned long long)__popcll(m));
-        if (b) atomicAdd(P.borrowed + fl, (unsigned long long)__popcll(b));
-    }
+    color_count1(A, P.borrowed, fl, filled, lent);
 }
 
 template <int CAMERA, int FILTER>
@@ -386,18 +229,14 @@ __global__ __launch_bounds__(256) void donor_gray16_kernel(DonorArgs P) {
         const int64_t g = donor_find<CAMERA>(P, A.luma, fl, A.width, A.height, A.out_width, u, v, &x, &y);
         uint32_t val = P.fill_y;
         if (g >= 0) {
-            val = donor_luma16<0, FILTER>(donor_plane(P, 0, g), A.src_pitch[0], (int)A.width, (int)A.height, x, y, 65535.0f);
+            val = sample_luma16<0, FILTER>(donor_plane(P, 0, g), A.src_pitch[0], (int)A.width, (int)A.height, x, y, 65535.0f);
             lent = g != (int64_t)P.f0 + fl;
         } else {
             filled = true;
         }
         color_store16(A.dst[0] + (size_t)fl * A.dst_stride[0] + (size_t)v * A.dst_pitch[0] + 2 * (size_t)u, val);
     }
-    const unsigned long long m = __ballot(filled), b = __ballot(lent);
-    if ((threadIdx.x & 63) == 0) {
-        if (m) atomicAdd(A.outside + fl, (unsigned long long)__popcll(m));
-        if (b) atomicAdd(P.borrowed + fl, (unsigned long long)__popcll(b));
-    }
+    color_count1(A, P.borrowed, fl, filled, lent);
 }
 
 } // namespace

@@ -100,6 +100,7 @@ using rs::f4;
 #include "kernels/features.hpp"
 #include "kernels/rectify.hpp"
 #include "kernels/stabilize.hpp"
+#include "kernels/colorsample.hpp"
 #include "kernels/color.hpp"
 #include "kernels/color16.hpp"
 #include "kernels/resample.hpp"
