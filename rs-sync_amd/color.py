@@ -25,9 +25,10 @@ import ctypes as C
 
 import numpy as np
 
-from .problem import RsSyncError, load_library
+from .problem import RsSyncError, product_library, product_only
 from .rectify import _check, _is_torch, _lens
 from .stabilize import StabilizeParams, _Cfg as _StabCfg, _targets, _times, params as _stab_params, CAMERA_LENS, DEFAULT_ITERATIONS
+from .stabilize import _launcher_cfg as _stab_launcher_cfg
 from .stabilize import FILTER_BILINEAR, FILTER_BICUBIC  # noqa: F401  (re-exported: stabilize_color(..., filter=FILTER_BICUBIC))
 
 _PD = C.POINTER(C.c_double)
@@ -74,27 +75,14 @@ SIGNATURES = {
     "rship_last_error": (C.c_char_p, [C.c_void_p]),
 }
 
-_BOUND = None
-
 
 def library():
     """the product library with the colour front's signatures attached"""
-    global _BOUND
-    lib = load_library()
-    if _BOUND is not lib:
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        _BOUND = lib
-    return lib
+    return product_library(SIGNATURES)
 
 
 def _lib_of(problem):
-    lib = library()
-    if problem._lib is not lib:
-        raise RsSyncError("the colour front runs in the product library only")
-    return lib
+    return product_only(problem, library(), "the colour front")
 
 
 def params(chroma_site=CHROMA_CENTER, fills=None, **kw):
@@ -247,39 +235,40 @@ def chroma_config(lens, width, height, out_width, out_height, chroma_site=CHROMA
     return lens_c, half(*cam), float(L[0] * (oy / height))
 
 
+def _launcher_cfg(problem, fmt, w, h, ow, oh, lens, delay, sigma, chroma_site, camera, iterations, fills, filter, zoom=1.0):
+    """rship_color_cfg for the *_budget calls of the internal launchers, as csrc/color_host.hpp resolves it: the luma
+    camera is the lens's scaled to the output, its focal lengths times `zoom` (1: a launcher that multiplies by a zoom per
+    frame itself); fills: None = the header's defaults for fill 0"""
+    if fills is None:
+        fills = (0, 0, 0, 255) if fmt == RGBA32 else (0, 128 << (DEPTH.get(fmt, 8) - 8), 128 << (DEPTH.get(fmt, 8) - 8), 0)
+    fill = 0 if fmt in SIBLING else fills[0]            # (16-bit: cfg.fill alone is read)
+    cfg = _Cfg()
+    cfg.luma = _stab_launcher_cfg(problem, w, h, ow, oh, lens, delay, sigma, camera, iterations, fill, filter, zoom=zoom)
+    cfg.chroma = cfg.luma
+    if SIBLING.get(fmt, fmt) in (NV12, I420):
+        lens_c, cam_c, cfg.chroma_time = chroma_config(lens, w, h, ow, oh, chroma_site, zoom=float(zoom))
+        cfg.chroma = _stab_launcher_cfg(problem, w // 2, h // 2, ow // 2, oh // 2, lens_c, delay, sigma, camera, iterations, fill, filter,
+                                        cam=cam_c)
+    cfg.format = int(fmt)
+    for k in range(4):
+        cfg.fill[k] = int(fills[k])
+    return cfg
+
+
 def stabilize_color_budget(problem, fmt, frames, frame_times, lens, delay, budget_bytes, out_size=None, sigma=0.0,
                            chroma_site=CHROMA_CENTER, iterations=DEFAULT_ITERATIONS, fills=None, filter=FILTER_BILINEAR):
     """stabilize_color along the path through the internal launcher with its device budget for the chunk slots given
     (tests: small frames that span several chunks).  LENS camera, zoom 1; fills: None = the header's defaults for fill 0.
     numpy frames -> (planes, n_outside (n, 2))"""
     lib = _lib_of(problem)
-    if fills is None:
-        fills = (0, 0, 0, 255) if fmt == RGBA32 else (0, 128 << (DEPTH.get(fmt, 8) - 8), 128 << (DEPTH.get(fmt, 8) - 8), 0)
     planes = _as_planes(fmt, frames)
     n, h, w = _size(fmt, planes)
     src, keep = _image(fmt, planes, n, h, w, False)
     t = _times(frame_times, n)
     L = _lens(lens)
     ow, oh = (w, h) if out_size is None else (int(out_size[0]), int(out_size[1]))
-    fs, start, n_knots = problem.gyro_info()
-    sx, sy = ow / w, oh / h
-    cam = (L[1] * sx, L[2] * sy, L[3] * sx, L[4] * sy)
-
-    def stab_cfg(w_, h_, ow_, oh_, lens_, cam_):
-        return _StabCfg(w_, h_, ow_, oh_, (C.c_double * 9)(*lens_), (C.c_double * 4)(*cam_), start, fs, n_knots, float(delay), float(sigma),
-                        CAMERA_LENS, int(iterations), 0 if fmt in SIBLING else int(fills[0]),    # (16-bit: cfg.fill alone is read)
-                        int(filter))
-
-    cfg = _Cfg()
-    cfg.luma = stab_cfg(w, h, ow, oh, L, cam)
-    cfg.chroma = cfg.luma
-    if SIBLING.get(fmt, fmt) in (NV12, I420):
-        lens_c, cam_c, cfg.chroma_time = chroma_config(L, w, h, ow, oh, chroma_site)
-        cfg.chroma = stab_cfg(w // 2, h // 2, ow // 2, oh // 2, lens_c, cam_c)
-    cfg.format = int(fmt)
-    for k in range(4):
-        cfg.fill[k] = int(fills[k])
-    res = [np.empty(s, np.uint16 if fmt in SIBLING else np.uint8) for s in plane_shapes(fmt, n, oh, ow)]
+    cfg = _launcher_cfg(problem, fmt, w, h, ow, oh, L, delay, sigma, chroma_site, CAMERA_LENS, iterations, fills, filter)
+    res =[np.empty(s, np.uint16 if fmt in SIBLING else np.uint8) for s in plane_shapes(fmt, n, oh, ow)]
     dst, okeep = _image(fmt, res, n, oh, ow, True)
     outside = np.zeros((max(n, 1), 2), np.uint64)
     ctx = C.c_void_p(problem.device_context())

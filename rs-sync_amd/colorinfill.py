@@ -15,11 +15,10 @@ import ctypes as C
 
 import numpy as np
 
-from .color import (CHROMA_CENTER, DEPTH, I420, NV12, RGBA32, SIBLING, ColorImage, ColorParams, _Cfg, _as_planes, _image, _out_like, _size,
-                    chroma_config, params)
-from .problem import RsSyncError, load_library
+from .color import CHROMA_CENTER, ColorImage, ColorParams, _Cfg, _as_planes, _image, _launcher_cfg, _out_like, _size, params
+from .problem import RsSyncError, product_library, product_only
 from .rectify import _check, _lens
-from .stabilize import CAMERA_LENS, DEFAULT_ITERATIONS, FILTER_BILINEAR, _Cfg as _StabCfg, _targets, _times
+from .stabilize import CAMERA_LENS, DEFAULT_ITERATIONS, FILTER_BILINEAR, _targets, _times
 
 _PD = C.POINTER(C.c_double)
 _PI = C.POINTER(ColorImage)
@@ -35,27 +34,14 @@ SIGNATURES = {
     "rship_last_error": (C.c_char_p, [C.c_void_p]),
 }
 
-_BOUND = None
-
 
 def library():
     """the product library with the colour infill's signatures attached"""
-    global _BOUND
-    lib = load_library()
-    if _BOUND is not lib:
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        _BOUND = lib
-    return lib
+    return product_library(SIGNATURES)
 
 
 def _lib_of(problem):
-    lib = library()
-    if problem._lib is not lib:
-        raise RsSyncError("the colour infill runs in the product library only")
-    return lib
+    return product_only(problem, library(), "the colour infill")
 
 
 def _counts(given, n, name):
@@ -103,30 +89,13 @@ def stabilize_color_infilled_budget(problem, fmt, frames, frame_times, lens, del
     frames that span several chunks, halos that cross chunk edges).  fills: None = the header's defaults for fill 0; targets:
     normalised here as the library normalises them.  -> (planes, n_outside (n, 2), n_borrowed (n, 2))"""
     lib = _lib_of(problem)
-    if fills is None:
-        fills = (0, 0, 0, 255) if fmt == RGBA32 else (0, 128 << (DEPTH.get(fmt, 8) - 8), 128 << (DEPTH.get(fmt, 8) - 8), 0)
     planes = _as_planes(fmt, frames)
     n, h, w = _size(fmt, planes)
     src, keep = _image(fmt, planes, n, h, w, False)
     t = _times(frame_times, n)
     L = _lens(lens)
     ow, oh = (w, h) if out_size is None else (int(out_size[0]), int(out_size[1]))
-    fs, start, n_knots = problem.gyro_info()
-
-    def stab_cfg(w_, h_, ow_, oh_, lens_, cam_):
-        return _StabCfg(w_, h_, ow_, oh_, (C.c_double * 9)(*lens_), (C.c_double * 4)(*cam_), start, fs, n_knots, float(delay), float(sigma),
-                        int(camera), int(iterations), 0 if fmt in SIBLING else int(fills[0]), int(filter))
-
-    sx, sy = ow / w, oh / h
-    cfg = _Cfg()
-    cfg.luma = stab_cfg(w, h, ow, oh, L, (L[1] * sx * float(zoom), L[2] * sy * float(zoom), L[3] * sx, L[4] * sy))
-    cfg.chroma = cfg.luma
-    if SIBLING.get(fmt, fmt) in (NV12, I420):
-        lens_c, cam_c, cfg.chroma_time = chroma_config(L, w, h, ow, oh, chroma_site, zoom=float(zoom))
-        cfg.chroma = stab_cfg(w // 2, h // 2, ow // 2, oh // 2, lens_c, cam_c)
-    cfg.format = int(fmt)
-    for k in range(4):
-        cfg.fill[k] = int(fills[k])
+    cfg = _launcher_cfg(problem, fmt, w, h, ow, oh, L, delay, sigma, chroma_site, camera, iterations, fills, filter, zoom=zoom)
     if targets is not None:             # (rs::limit_unit's operations in its order: the launcher takes unit quaternions)
         q = np.array(targets, np.float64)
         targets = q / np.sqrt(((q[:, 0] * q[:, 0] + q[:, 1] * q[:, 1]) + q[:, 2] * q[:, 2]) + q[:, 3] * q[:, 3])[:, None]

@@ -49,6 +49,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #ifndef RSSYNC_TEST_VARIANTS
@@ -3756,16 +3757,24 @@ int rect_rays_into(rship_ctx* c, const rship_rectify_cfg* g, DevBuf& rays, doubl
 
 int rect_rays(rship_ctx* c, const rship_rectify_cfg* g) { return rect_rays_into(c, g, c->rect_rays, c->rect_key, c->rect_rays_ok); }
 
-RectRowsArgs rect_rows_args(rship_ctx* c, const rship_rectify_cfg* g) {
-    RectRowsArgs R{};
+// what the arguments of every rows kernel share (Rows: Rect-, Stab-, Color-, Infill- or DonorRowsArgs), from the rectifier's
+// or the stabiliser's configuration
+template <class Rows, class Cfg>
+Rows rows_args(rship_ctx* c, const Cfg* g) {
+    Rows R{};
     R.table = (const double*)c->coef64.p;
     R.start = g->start;
     R.fs = g->fs;
     R.ro = g->lens[0];
     R.delay = g->delay;
-    R.ref_row = g->ref_row;
     R.n_knots = c->n_knots;
     R.rows = g->height;
+    return R;
+}
+
+RectRowsArgs rect_rows_args(rship_ctx* c, const rship_rectify_cfg* g) {
+    RectRowsArgs R = rows_args<RectRowsArgs>(c, g);
+    R.ref_row = g->ref_row;
     return R;
 }
 
@@ -3887,6 +3896,40 @@ int frame_pipeline(rship_ctx* c, const rs::FramePlan& P, int np, const rship_col
     return sync_stream(c);
 }
 
+// The set-up of a call with one 8-bit plane per frame, w x h in and ow x oh out, and its chunks through frame_pipeline: the
+// checks of the caller's pointers, pitches and strides (`who` names the front door in the messages, out_name its output),
+// the plan with 2 radius + 1 tables per frame and the halo, the frames' times in c->rect_times and `runs` zeroed counts
+// per frame in c->rect_count, which go to `counts` (host; NULL: none) at the end.  ready() enqueues what the kernels need
+// besides (targets, ray map) and fills their arguments; per_chunk(K, dev_in) is frame_pipeline's, dev_in: the frames are
+// device memory.
+template <class Ready, class PerChunk>
+int gray_frames_call(rship_ctx* c, const char* who, const char* out_name, const rship_color_image& in, uint32_t w, uint32_t h,
+                     const rship_color_image& out, uint32_t ow, uint32_t oh, uint32_t n_frames, const double* frame_times, size_t budget_bytes,
+                     uint32_t radius, size_t runs, uint64_t* counts, Ready&& ready, PerChunk&& per_chunk) {
+    if (!in.plane[0] || !out.plane[0] || !frame_times) return set_err(c, std::string(who) + ": null pointer");
+    if (!n_frames) return 0;
+    if (in.pitch[0] < w || out.pitch[0] < ow || (n_frames > 1 && (in.stride[0] < in.pitch[0] * h || out.stride[0] < out.pitch[0] * oh)))
+        return set_err(c, std::string(who) + ": pitch or frame stride too small");
+    bool dev_in = false, dev_out = false;
+    if (rect_pointer(c, in.plane[0], "the frames", &dev_in, who) || rect_pointer(c, out.plane[0], out_name, &dev_out, who)) return 1;
+    // the chunk: per output frame its tables, its input and its output; per slot the halo's input frames besides
+    const rs::FramePlan P = gray_plan(n_frames, budget_bytes, 2 * radius + 1, radius, w, h, dev_in, ow, oh, dev_out);
+    if (ensure(c, c->rect_times, (size_t)n_frames * 8) || ensure(c, c->rect_count, runs * n_frames * 8)) return 1;
+    RS_HIP(hipMemcpy(c->rect_times.p, frame_times, (size_t)n_frames * 8, hipMemcpyHostToDevice));
+    RS_HIP(hipMemsetAsync(c->rect_count.p, 0, runs * n_frames * 8, c->stream));
+    if (ready()) return 1;
+    return frame_pipeline(c, P, 1, in, out, counts, runs * n_frames, [&](const FrameChunk& K) -> int { return per_chunk(K, dev_in); });
+}
+
+// the chunk's tables, its counts of filled pixels and its plane 0 in the arguments of a kernel with one plane per frame
+template <class Args>
+void gray_chunk_args(rship_ctx* c, Args& A, const FrameChunk& K) {
+    A.rows_tab = (const float*)K.base;
+    A.outside = (unsigned long long*)c->rect_count.p + K.f0;
+    A.src = K.src[0]; A.src_pitch = K.src_pitch[0]; A.src_stride = K.src_stride[0];
+    A.dst = K.dst[0]; A.dst_pitch = K.dst_pitch[0]; A.dst_stride = K.dst_stride[0];
+}
+
 } // namespace
 
 extern "C" {
@@ -3896,31 +3939,21 @@ int rship_rectify_frames(rship_ctx* c, const uint8_t* frames, uint32_t n_frames,
                          uint64_t* n_outside, size_t budget_bytes) {
     DeviceGuard dev_guard(c);
     if (rect_check(c, cfg)) return 1;
-    if (!frames || !out || !frame_times) return set_err(c, "rectify: null pointer");
-    if (!n_frames) return 0;
     const uint32_t w = cfg->width, h = cfg->height;
-    if (pitch < w || out_pitch < w || (n_frames > 1 && (frame_stride < pitch * h || out_stride < out_pitch * h)))
-        return set_err(c, "rectify: pitch or frame stride too small");
-    bool dev_in = false, dev_out = false;
-    if (rect_pointer(c, frames, "the frames", &dev_in) || rect_pointer(c, out, "the rectified frames", &dev_out)) return 1;
-    const rs::FramePlan P = gray_plan(n_frames, budget_bytes, 1, 0, w, h, dev_in, w, h, dev_out);
-    if (ensure(c, c->rect_times, (size_t)n_frames * 8) || ensure(c, c->rect_count, (size_t)n_frames * 8)) return 1;
-    RS_HIP(hipMemcpy(c->rect_times.p, frame_times, (size_t)n_frames * 8, hipMemcpyHostToDevice));
-    RS_HIP(hipMemsetAsync(c->rect_count.p, 0, (size_t)n_frames * 8, c->stream));
-    if (rect_rays(c, cfg)) return 1;
     RectRowsArgs R = rect_rows_args(c, cfg);
-    RectArgs A = rect_args(c, cfg);
-    return frame_pipeline(c, P, 1, gray_image(frames, pitch, frame_stride), gray_image(out, out_pitch, out_stride), n_outside, n_frames,
-                          [&](const FrameChunk& K) -> int {
+    RectArgs A{};
+    return gray_frames_call(c, "rectify", "the rectified frames", gray_image(frames, pitch, frame_stride), w, h, gray_image(out, out_pitch, out_stride),
+                            w, h, n_frames, frame_times, budget_bytes, 0, 1, n_outside, [&]() -> int {
+        if (rect_rays(c, cfg)) return 1;
+        A = rect_args(c, cfg);
+        return 0;
+    }, [&](const FrameChunk& K, bool) -> int {
         R.times = (const double*)c->rect_times.p + K.f0;
         R.rows_tab = (float*)K.base;
         R.n_frames = K.cnt;
         hipLaunchKernelGGL(rectify_rows_kernel, dim3((h + 1 + 255) / 256, K.cnt), dim3(256), 0, c->stream, R);
         RS_HIP(hipGetLastError());
-        A.rows_tab = (const float*)K.base;
-        A.outside = (unsigned long long*)c->rect_count.p + K.f0;
-        A.src = K.src[0]; A.src_pitch = K.src_pitch[0]; A.src_stride = K.src_stride[0];
-        A.dst = K.dst[0]; A.dst_pitch = K.dst_pitch[0]; A.dst_stride = K.dst_stride[0];
+        gray_chunk_args(c, A, K);
         hipLaunchKernelGGL(rectify_kernel<false>, dim3((w + kRectTW - 1) / kRectTW, (h + kRectTH - 1) / kRectTH, K.cnt), dim3(256), 0, c->stream, A);
         RS_HIP(hipGetLastError());
         return 0;
@@ -4058,18 +4091,6 @@ int stab_fill_targets(rship_ctx* c, const rship_stabilize_cfg* g, const double* 
     return 0;
 }
 
-StabRowsArgs stab_rows_args(rship_ctx* c, const rship_stabilize_cfg* g) {
-    StabRowsArgs R{};
-    R.table = (const double*)c->coef64.p;
-    R.start = g->start;
-    R.fs = g->fs;
-    R.ro = g->lens[0];
-    R.delay = g->delay;
-    R.n_knots = c->n_knots;
-    R.rows = g->height;
-    return R;
-}
-
 rs::RectLensF stab_lens_f(const rship_stabilize_cfg* g) {
     return rs::RectLensF{(float)g->lens[1], (float)g->lens[2], (float)g->lens[3], (float)g->lens[4],
                          (float)g->lens[5], (float)g->lens[6], (float)g->lens[7], (float)g->lens[8]};
@@ -4122,32 +4143,23 @@ template <class Launch>
 int stab_frames_run(rship_ctx* c, const uint8_t* frames, uint32_t n_frames, size_t pitch, size_t frame_stride, const double* frame_times,
                     const double* targets, const rship_stabilize_cfg* cfg, uint8_t* out, size_t out_pitch, size_t out_stride,
                     uint64_t* n_outside, size_t budget_bytes, bool ray_map, Launch&& launch) {
-    if (!frames || !out || !frame_times) return set_err(c, "stabilize: null pointer");
-    if (!n_frames) return 0;
-    const uint32_t w = cfg->width, h = cfg->height, ow = cfg->out_width, oh = cfg->out_height;
-    if (pitch < w || out_pitch < ow || (n_frames > 1 && (frame_stride < pitch * h || out_stride < out_pitch * oh)))
-        return set_err(c, "stabilize: pitch or frame stride too small");
-    bool dev_in = false, dev_out = false;
-    if (rect_pointer(c, frames, "the frames", &dev_in, "stabilize") || rect_pointer(c, out, "the stabilised frames", &dev_out, "stabilize")) return 1;
-    const rs::FramePlan P = gray_plan(n_frames, budget_bytes, 1, 0, w, h, dev_in, ow, oh, dev_out);
-    if (ensure(c, c->rect_times, (size_t)n_frames * 8) || ensure(c, c->rect_count, (size_t)n_frames * 8)) return 1;
-    RS_HIP(hipMemcpy(c->rect_times.p, frame_times, (size_t)n_frames * 8, hipMemcpyHostToDevice));
-    RS_HIP(hipMemsetAsync(c->rect_count.p, 0, (size_t)n_frames * 8, c->stream));
-    if (stab_fill_targets(c, cfg, targets, n_frames) || (ray_map && stab_rays(c, cfg))) return 1;
-    StabRowsArgs R = stab_rows_args(c, cfg);
-    StabArgs A = stab_args(c, cfg);
-    return frame_pipeline(c, P, 1, gray_image(frames, pitch, frame_stride), gray_image(out, out_pitch, out_stride), n_outside, n_frames,
-                          [&](const FrameChunk& K) -> int {
+    const uint32_t h = cfg->height;
+    StabRowsArgs R = rows_args<StabRowsArgs>(c, cfg);
+    StabArgs A{};
+    return gray_frames_call(c, "stabilize", "the stabilised frames", gray_image(frames, pitch, frame_stride), cfg->width, h,
+                            gray_image(out, out_pitch, out_stride), cfg->out_width, cfg->out_height, n_frames, frame_times, budget_bytes, 0, 1,
+                            n_outside, [&]() -> int {
+        if (stab_fill_targets(c, cfg, targets, n_frames) || (ray_map && stab_rays(c, cfg))) return 1;
+        A = stab_args(c, cfg);
+        return 0;
+    }, [&](const FrameChunk& K, bool) -> int {
         R.times = (const double*)c->rect_times.p + K.f0;
         R.targets = (const double*)c->stab_targets.p + (size_t)K.f0 * 4;
         R.rows_tab = (float*)K.base;
         R.n_frames = K.cnt;
         hipLaunchKernelGGL(stabilize_rows_kernel, dim3((h + 1 + 255) / 256, K.cnt), dim3(256), 0, c->stream, R);
         RS_HIP(hipGetLastError());
-        A.rows_tab = (const float*)K.base;
-        A.outside = (unsigned long long*)c->rect_count.p + K.f0;
-        A.src = K.src[0]; A.src_pitch = K.src_pitch[0]; A.src_stride = K.src_stride[0];
-        A.dst = K.dst[0]; A.dst_pitch = K.dst_pitch[0]; A.dst_stride = K.dst_stride[0];
+        gray_chunk_args(c, A, K);
         launch(A, K.f0, K.cnt);
         RS_HIP(hipGetLastError());
         return 0;
@@ -4161,7 +4173,7 @@ int stab_map_run(rship_ctx* c, const rship_stabilize_cfg* g, const DevBuf& rays,
     const uint32_t h = g->height;
     const size_t n = (size_t)g->out_width * g->out_height;
     if (ensure(c, c->rect_slot[0], (size_t)(h + 1) * 9 * sizeof(float)) || (!on_dev && ensure(c, c->rect_tmp, n * sizeof(float2)))) return 1;
-    StabRowsArgs R = stab_rows_args(c, g);
+    StabRowsArgs R = rows_args<StabRowsArgs>(c, g);
     R.times = (const double*)c->rect_times.p + time_at;
     R.targets = (const double*)c->stab_targets.p;
     R.rows_tab = (float*)c->rect_slot[0].p;
@@ -4176,6 +4188,40 @@ int stab_map_run(rship_ctx* c, const rship_stabilize_cfg* g, const DevBuf& rays,
     RS_HIP(hipGetLastError());
     if (!on_dev) RS_HIP(hipMemcpyAsync(map_xy, c->rect_tmp.p, n * sizeof(float2), hipMemcpyDeviceToHost, c->stream));
     return sync_stream(c);
+}
+
+// c->stab_zooms <- the cameras of all frames, fp64 products as the configuration holds them for a constant zoom: per frame
+// (fx zoom, fy zoom) and, with per == 4, the chroma camera's, the same times 0.5 (color_chroma_camera).  `bad`: the
+// caller's message for a zoom that is not finite and > 0
+int zoom_cams(rship_ctx* c, const rship_stabilize_cfg* g, const double* zooms, uint32_t n_frames, size_t per, const char* bad) {
+    std::vector<double> cams((size_t)n_frames * per);
+    for (uint32_t f = 0; f < n_frames; ++f) {
+        if (!(zooms[f] > 0.0) || !std::isfinite(zooms[f])) return set_err(c, bad);
+        double* k = &cams[per * (size_t)f];
+        k[0] = g->cam[0] * zooms[f];
+        k[1] = g->cam[1] * zooms[f];
+        if (per == 4) {
+            k[2] = k[0] * 0.5;
+            k[3] = k[1] * 0.5;
+        }
+    }
+    if (n_frames) {
+        if (ensure(c, c->stab_zooms, cams.size() * 8)) return 1;
+        RS_HIP(hipMemcpy(c->stab_zooms.p, cams.data(), cams.size() * 8, hipMemcpyHostToDevice));
+    }
+    return 0;
+}
+
+// zoom_render_kernel's arguments of a call, all but the chunk's: the rest of the output camera
+ZoomRenderArgs zoom_render_args(const rship_stabilize_cfg* g) {
+    ZoomRenderArgs Z{};
+    Z.cx = g->cam[2];
+    Z.cy = g->cam[3];
+    Z.k1 = g->lens[5];
+    Z.k2 = g->lens[6];
+    Z.k3 = g->lens[7];
+    Z.k4 = g->lens[8];
+    return Z;
 }
 
 } // namespace
@@ -4236,7 +4282,7 @@ int rship_stabilize_coverage(rship_ctx* c, const double* frame_times, uint32_t n
     RS_HIP(hipMemcpy(c->stab_zooms.p, zooms, (size_t)n_zooms * 8, hipMemcpyHostToDevice));
     RS_HIP(hipMemsetAsync(c->stab_cover.p, 0, counts, c->stream));
     if (stab_fill_targets(c, cfg, targets, n_frames)) return 1;
-    StabRowsArgs R = stab_rows_args(c, cfg);
+    StabRowsArgs R = rows_args<StabRowsArgs>(c, cfg);
     R.rows_tab = (float*)c->rect_slot[0].p;
     StabCoverArgs V{};
     V.rows_tab = (const float*)c->rect_slot[0].p;
@@ -4292,7 +4338,7 @@ int rship_zoom_fit(rship_ctx* c, const double* frame_times, uint32_t n_frames, c
         return 1;
     RS_HIP(hipMemcpy(c->rect_times.p, frame_times, (size_t)n_frames * 8, hipMemcpyHostToDevice));
     if (stab_fill_targets(c, cfg, targets, n_frames)) return 1;
-    StabRowsArgs R = stab_rows_args(c, cfg);
+    StabRowsArgs R = rows_args<StabRowsArgs>(c, cfg);
     R.rows_tab = (float*)c->rect_slot[0].p;
     ZoomFitArgs Z{};
     Z.rows_tab = (const float*)c->rect_slot[0].p;
@@ -4333,24 +4379,8 @@ int rship_zoom_frames(rship_ctx* c, const uint8_t* frames, uint32_t n_frames, si
     DeviceGuard dev_guard(c);
     if (stab_check(c, cfg)) return 1;
     if (!zooms) return set_err(c, "zoom: null pointer");
-    // the cameras of all frames: (fx zoom, fy zoom), fp64 products as the stabiliser's configuration holds them
-    std::vector<double> cams((size_t)n_frames * 2);
-    for (uint32_t f = 0; f < n_frames; ++f) {
-        if (!(zooms[f] > 0.0) || !std::isfinite(zooms[f])) return set_err(c, "zoom: every zoom must be finite and > 0");
-        cams[2 * (size_t)f] = cfg->cam[0] * zooms[f];
-        cams[2 * (size_t)f + 1] = cfg->cam[1] * zooms[f];
-    }
-    if (n_frames) {
-        if (ensure(c, c->stab_zooms, cams.size() * 8)) return 1;
-        RS_HIP(hipMemcpy(c->stab_zooms.p, cams.data(), cams.size() * 8, hipMemcpyHostToDevice));
-    }
-    ZoomRenderArgs Z{};
-    Z.cx = cfg->cam[2];
-    Z.cy = cfg->cam[3];
-    Z.k1 = cfg->lens[5];
-    Z.k2 = cfg->lens[6];
-    Z.k3 = cfg->lens[7];
-    Z.k4 = cfg->lens[8];
+    if (zoom_cams(c, cfg, zooms, n_frames, 2, "zoom: every zoom must be finite and > 0")) return 1;
+    ZoomRenderArgs Z = zoom_render_args(cfg);
     return stab_frames_run(c, frames, n_frames, pitch, frame_stride, frame_times, targets, cfg, out, out_pitch, out_stride, n_outside, budget_bytes,
                            false, [&](const StabArgs& A, uint32_t f0, uint32_t cnt) {
                                Z.S = A;
@@ -4561,7 +4591,84 @@ ColorLaunch color_launch(rship_ctx* c, const rship_color_cfg* cfg, const rship_s
     return K;
 }
 
-// The frames of rship_color_frames and rship_colorzoom_frames through frame_pipeline.  launch(K, f0, cnt) enqueues the
+// the luma plane's configuration with the call's fill (the 16-bit kernels take their fills as arguments of their own)
+rship_stabilize_cfg color_luma(const rship_color_cfg* cfg) {
+    rship_stabilize_cfg L = cfg->luma;
+    if (!color_is_16(cfg->format)) L.fill = cfg->fill[0];
+    return L;
+}
+
+// count runs 2 j and 2 j + 1 of n entries each, the luma's and the chroma's, go to the caller's pairs[j] as (luma, chroma)
+// pairs (NULL: not wanted)
+void pair_counts(const std::vector<uint64_t>& counts, size_t n, uint64_t* const* pairs, size_t n_pairs) {
+    for (size_t j = 0; j < n_pairs && !counts.empty(); ++j)
+        for (size_t k = 0; pairs[j] && k < n; ++k) {
+            pairs[j][2 * k] = counts[2 * j * n + k];
+            pairs[j][2 * k + 1] = counts[(2 * j + 1) * n + k];
+        }
+}
+
+// The set-up every colour call shares (n_frames >= 1), and its chunks through frame_pipeline: the images' checks and the
+// plan with 2 radius + 1 tables per frame and region and the halo; the frames' times, then the chroma planes', in
+// c->rect_times; two zeroed count runs per entry of `pairs` in c->rect_count (filled plane 0, filled chroma, then the
+// caller's own), which go to the caller in pairs at the end; the targets and, with ray_maps, the cached ray maps of cfg's
+// output cameras.  Per chunk the rows arguments R get what all rows kernels share and the chunk's tables, the colour
+// arguments K.A the tables, the counts of filled samples and the chunk's planes; per_chunk(C, R, K, dev_in) enqueues the
+// chunk's rows kernel and render kernel, dev_in: the input is device memory.
+template <class Rows, class PerChunk>
+int color_call(rship_ctx* c, const rship_color_image* in, uint32_t n_frames, const double* frame_times, const double* targets,
+               const rship_color_cfg* cfg, const rship_color_image* out, size_t budget_bytes, uint32_t radius, bool ray_maps,
+               uint64_t* const* pairs, size_t n_pairs, PerChunk&& per_chunk) {
+    const rship_stabilize_cfg L = color_luma(cfg);
+    const bool yuv = color_is_yuv(cfg->format);
+    const size_t n = n_frames, runs = 2 * n_pairs;
+    rs::FrameLayout q;
+    int np = 0;
+    bool dev_in = false;
+    if (color_layout(c, in, n_frames, cfg, out, budget_bytes, &q, &np, &dev_in)) return 1;
+    // the chunk: per output frame its tables of both regions, its input and its output planes; per slot the halo's input
+    // frames besides
+    q.tabs = 2 * radius + 1;
+    q.radius = radius;
+    const rs::FramePlan P = rs::plan_frames(q);
+    if (ensure(c, c->rect_times, n * 16) || ensure(c, c->rect_count, runs * n * 8)) return 1;
+    std::vector<double> times(2 * n);
+    for (size_t k = 0; k < n; ++k) {
+        times[k] = frame_times[k];
+        times[n + k] = frame_times[k] + cfg->chroma_time;
+    }
+    RS_HIP(hipMemcpy(c->rect_times.p, times.data(), times.size() * 8, hipMemcpyHostToDevice));
+    RS_HIP(hipMemsetAsync(c->rect_count.p, 0, runs * n * 8, c->stream));
+    if (stab_fill_targets(c, &L, targets, n) || (ray_maps && (stab_rays(c, &L) || (yuv && stab_rays(c, &cfg->chroma, true))))) return 1;
+    Rows R = rows_args<Rows>(c, &L);
+    R.rows_c = yuv ? L.height / 2 : 0;
+    ColorLaunch K = color_launch(c, cfg, L);
+    ColorArgs& A = K.A;
+    // every count run in one download
+    const bool wanted = std::any_of(pairs, pairs + n_pairs, [](const uint64_t* p) { return p != nullptr; });
+    std::vector<uint64_t> counts(wanted ? runs * n : 0);
+    if (frame_pipeline(c, P, np, *in, *out, wanted ? counts.data() : nullptr, counts.size(), [&](const FrameChunk& C) -> int {
+            R.rows_tab = (float*)(C.base + P.off_tab[0]);
+            R.rows_tab_c = (float*)(C.base + P.off_tab[1]);
+            A.luma.rows_tab = R.rows_tab;
+            A.chroma.rows_tab = R.rows_tab_c;
+            A.outside = (unsigned long long*)c->rect_count.p + C.f0;
+            A.outside_c = A.outside + n;
+            for (int k = 0; k < np; ++k) {
+                A.src[k] = C.src[k]; A.src_pitch[k] = C.src_pitch[k]; A.src_stride[k] = C.src_stride[k];
+                A.dst[k] = C.dst[k]; A.dst_pitch[k] = C.dst_pitch[k]; A.dst_stride[k] = C.dst_stride[k];
+            }
+            return per_chunk(C, R, K, dev_in);
+        }))
+        return 1;
+    pair_counts(counts, n, pairs, n_pairs);
+    return 0;
+}
+
+// the x extent of a colour rows launch: the luma table's entries, then the chroma table's
+uint32_t color_rows_blocks(uint32_t rows, uint32_t rows_c) { return (rows + 1 + (rows_c ? rows_c + 1 : 0) + 255) / 256; }
+
+// The frames of rship_color_frames and rship_colorzoom_frames through color_call.  launch(K, f0, cnt) enqueues the
 // kernel that renders the chunk's cnt frames, the first of which is frame f0 of the call; ray_maps: the cached ray maps of
 // cfg's output cameras are needed.
 template <class Launch>
@@ -4570,83 +4677,82 @@ int color_frames_run(rship_ctx* c, const rship_color_image* in, uint32_t n_frame
                      Launch&& launch) {
     if (!in || !out || !frame_times) return set_err(c, "color: null pointer");
     if (!n_frames) return 0;
-    rship_stabilize_cfg L = cfg->luma;
-    if (!color_is_16(cfg->format)) L.fill = cfg->fill[0]; // (the 16-bit kernels take their fills as arguments of their own)
-    const bool yuv = color_is_yuv(cfg->format);
-    const uint32_t h = L.height, hc = yuv ? h / 2 : 0;
-    rs::FrameLayout q;
-    int np = 0;
-    bool dev_in = false;
-    if (color_layout(c, in, n_frames, cfg, out, budget_bytes, &q, &np, &dev_in)) return 1;
-    const rs::FramePlan P = rs::plan_frames(q);
-    if (ensure(c, c->rect_times, (size_t)n_frames * 16) || ensure(c, c->rect_count, (size_t)n_frames * 16)) return 1;
-    // the frames' times, then the chroma planes'; the filled pixels of plane 0, then the filled chroma samples
-    std::vector<double> times(2 * (size_t)n_frames);
-    for (uint32_t k = 0; k < n_frames; ++k) {
-        times[k] = frame_times[k];
-        times[n_frames + k] = frame_times[k] + cfg->chroma_time;
-    }
-    RS_HIP(hipMemcpy(c->rect_times.p, times.data(), times.size() * 8, hipMemcpyHostToDevice));
-    RS_HIP(hipMemsetAsync(c->rect_count.p, 0, (size_t)n_frames * 16, c->stream));
-    if (stab_fill_targets(c, &L, targets, n_frames) || (ray_maps && (stab_rays(c, &L) || (yuv && stab_rays(c, &cfg->chroma, true))))) return 1;
-    ColorRowsArgs R{};
-    R.table = (const double*)c->coef64.p;
-    R.start = L.start;
-    R.fs = L.fs;
-    R.ro = L.lens[0];
-    R.delay = L.delay;
-    R.n_knots = c->n_knots;
-    R.rows = h;
-    R.rows_c = hc;
-    ColorLaunch K = color_launch(c, cfg, L);
-    StabArgs& G = K.G;
-    ColorArgs& A = K.A;
-    // the filled pixels of plane 0 and the filled chroma samples come back as two runs and go to the caller in pairs
-    std::vector<uint64_t> counts(n_outside ? 2 * (size_t)n_frames : 0);
-    if (frame_pipeline(c, P, np, *in, *out, n_outside ? counts.data() : nullptr, counts.size(), [&](const FrameChunk& C) -> int {
-            const uint32_t f0 = C.f0, cnt = C.cnt;
-            R.times = (const double*)c->rect_times.p + f0;
-            R.times_c = (const double*)c->rect_times.p + n_frames + f0;
-            R.targets = (const double*)c->stab_targets.p + (size_t)f0 * 4;
-            R.rows_tab = (float*)(C.base + P.off_tab[0]);
-            R.rows_tab_c = (float*)(C.base + P.off_tab[1]);
-            R.n_frames = cnt;
-            hipLaunchKernelGGL(color_rows_kernel, dim3((h + 1 + (yuv ? hc + 1 : 0) + 255) / 256, cnt), dim3(256), 0, c->stream, R);
-            RS_HIP(hipGetLastError());
-            A.luma.rows_tab = R.rows_tab;
-            A.chroma.rows_tab = R.rows_tab_c;
-            A.outside = (unsigned long long*)c->rect_count.p + f0;
-            A.outside_c = (unsigned long long*)c->rect_count.p + n_frames + f0;
-            for (int k = 0; k < np; ++k) {
-                A.src[k] = C.src[k]; A.src_pitch[k] = C.src_pitch[k]; A.src_stride[k] = C.src_stride[k];
-                A.dst[k] = C.dst[k]; A.dst_pitch[k] = C.dst_pitch[k]; A.dst_stride[k] = C.dst_stride[k];
-            }
-            if (cfg->format == 0) {
-                G.rows_tab = A.luma.rows_tab;
-                G.outside = A.outside;
-                G.src = A.src[0]; G.src_pitch = A.src_pitch[0]; G.src_stride = A.src_stride[0];
-                G.dst = A.dst[0]; G.dst_pitch = A.dst_pitch[0]; G.dst_stride = A.dst_stride[0];
-            }
-            launch(K, f0, cnt);
-            RS_HIP(hipGetLastError());
-            return 0;
-        }))
-        return 1;
-    for (size_t k = 0; k < counts.size() / 2; ++k) {
-        n_outside[2 * k] = counts[k];
-        n_outside[2 * k + 1] = counts[n_frames + k];
-    }
-    return 0;
+    return color_call<ColorRowsArgs>(c, in, n_frames, frame_times, targets, cfg, out, budget_bytes, 0, ray_maps, &n_outside, 1,
+                                     [&](const FrameChunk& C, ColorRowsArgs& R, ColorLaunch& K, bool) -> int {
+        R.times = (const double*)c->rect_times.p + C.f0;
+        R.times_c = R.times + n_frames;
+        R.targets = (const double*)c->stab_targets.p + (size_t)C.f0 * 4;
+        R.n_frames = C.cnt;
+        hipLaunchKernelGGL(color_rows_kernel, dim3(color_rows_blocks(R.rows, R.rows_c), C.cnt), dim3(256), 0, c->stream, R);
+        RS_HIP(hipGetLastError());
+        if (cfg->format == 0) gray_chunk_args(c, K.G, C); // GRAY8: the stabiliser's kernel
+        launch(K, C.f0, C.cnt);
+        RS_HIP(hipGetLastError());
+        return 0;
+    });
 }
 
-// F: the linear kernel of a format, or its cubic sibling of kernels/resample.hpp
-template <int C, int F> struct PickNv12 { static constexpr auto kernel = F ? bicubic_yuv_kernel<C, true> : color_yuv_kernel<C, true>; };
-template <int C, int F> struct PickI420 { static constexpr auto kernel = F ? bicubic_yuv_kernel<C, false> : color_yuv_kernel<C, false>; };
-template <int C, int F> struct PickRgba { static constexpr auto kernel = F ? bicubic_rgba_kernel<C> : color_rgba_kernel<C>; };
-template <int C, int F> struct PickGray16 { static constexpr auto kernel = F ? bicubic16_gray_kernel<C> : color16_gray_kernel<C>; };
-template <int C, int F> struct PickP010 { static constexpr auto kernel = F ? bicubic16_yuv_kernel<C, true, 6> : color16_yuv_kernel<C, true, 6>; };
-template <int C, int F> struct PickP016 { static constexpr auto kernel = F ? bicubic16_yuv_kernel<C, true, 0> : color16_yuv_kernel<C, true, 0>; };
-template <int C, int F> struct PickI010 { static constexpr auto kernel = F ? bicubic16_yuv_kernel<C, false, 0> : color16_yuv_kernel<C, false, 0>; };
+// ---- one format dispatch ----------------------------------------------------------------------------------------------
+// A family: the render kernels of a colour front door by format, as the members yuv8<C, NV, F> (NV12, I420), rgba8<C, F>,
+// gray16<C, F> and yuv16<C, NV, SH, F> (P010: SH 6; P016, I010), C the camera and F the filter, and
+// launch<Pick>(c, camera, filter, grid, args...), which gives a member the arguments it takes.
+
+// the launch of a family whose kernels all take the caller's arguments as they are
+struct FamilyLaunch {
+    template <template <int, int> class Pick, class... Args>
+    static void launch(rship_ctx* c, int camera, int filter, dim3 grid, const Args&... args) {
+        camfilt_launch<Pick>(c, camera, filter, grid, args...);
+    }
+};
+
+// the member of a family that a format has, as camfilt_launch's Pick<C, F>
+template <class Fam>
+struct FormatPick {
+    template <int C, int F> struct Nv12 { static constexpr auto kernel = Fam::template yuv8<C, true, F>; };
+    template <int C, int F> struct I420 { static constexpr auto kernel = Fam::template yuv8<C, false, F>; };
+    template <int C, int F> struct Rgba { static constexpr auto kernel = Fam::template rgba8<C, F>; };
+    template <int C, int F> struct Gray16 { static constexpr auto kernel = Fam::template gray16<C, F>; };
+    template <int C, int F> struct P010 { static constexpr auto kernel = Fam::template yuv16<C, true, 6, F>; };
+    template <int C, int F> struct P016 { static constexpr auto kernel = Fam::template yuv16<C, true, 0, F>; };
+    template <int C, int F> struct I010 { static constexpr auto kernel = Fam::template yuv16<C, false, 0, F>; };
+};
+
+// cnt frames of ow x oh pixels through the family's kernel of the format (not GRAY8: the gray kernels'), the camera and the
+// filter; a 4:2:0 format runs on the chroma plane's grid
+template <class Fam, class... Args>
+void format_launch(rship_ctx* c, int format, int camera, int filter, uint32_t ow, uint32_t oh, uint32_t cnt, const Args&... args) {
+    using M = FormatPick<Fam>;
+    const uint32_t gw = color_is_yuv(format) ? ow / 2 : ow, gh = color_is_yuv(format) ? oh / 2 : oh;
+    const dim3 grid((gw + kRectTW - 1) / kRectTW, (gh + kRectTH - 1) / kRectTH, cnt);
+    switch (format) {
+    case 1: Fam::template launch<M::template Nv12>(c, camera, filter, grid, args...); break;
+    case 2: Fam::template launch<M::template I420>(c, camera, filter, grid, args...); break;
+    case 3: Fam::template launch<M::template Rgba>(c, camera, filter, grid, args...); break;
+    case 16: Fam::template launch<M::template Gray16>(c, camera, filter, grid, args...); break;
+    case 17: Fam::template launch<M::template P010>(c, camera, filter, grid, args...); break;
+    case 18: Fam::template launch<M::template P016>(c, camera, filter, grid, args...); break;
+    case 19: Fam::template launch<M::template I010>(c, camera, filter, grid, args...); break;
+    }
+}
+
+// The constant camera's family.  F: the linear kernel of a format, or its cubic sibling of kernels/resample.hpp; the
+// 16-bit kernels take their fills as arguments of their own, gray16 the luma's and yuv16 both.
+struct ColorFamily {
+    template <int C, bool NV, int F> static constexpr auto yuv8 = F ? bicubic_yuv_kernel<C, NV> : color_yuv_kernel<C, NV>;
+    template <int C, int F> static constexpr auto rgba8 = F ? bicubic_rgba_kernel<C> : color_rgba_kernel<C>;
+    template <int C, int F> static constexpr auto gray16 = F ? bicubic16_gray_kernel<C> : color16_gray_kernel<C>;
+    template <int C, bool NV, int SH, int F>
+    static constexpr auto yuv16 = F ? bicubic16_yuv_kernel<C, NV, SH> : color16_yuv_kernel<C, NV, SH>;
+
+    template <template <int, int> class Pick>
+    static void launch(rship_ctx* c, int camera, int filter, dim3 grid, const ColorLaunch& K) {
+        using Kernel = decltype(Pick<0, 0>::kernel);
+        if constexpr (std::is_invocable_v<Kernel, ColorArgs, uint32_t, uint32_t>)
+            camfilt_launch<Pick>(c, camera, filter, grid, K.A, K.fill16_y, K.fill16_uv);
+        else if constexpr (std::is_invocable_v<Kernel, ColorArgs, uint32_t>) camfilt_launch<Pick>(c, camera, filter, grid, K.A, K.fill16_y);
+        else camfilt_launch<Pick>(c, camera, filter, grid, K.A);
+    }
+};
 
 } // namespace
 
@@ -4656,24 +4762,11 @@ int rship_color_frames(rship_ctx* c, const rship_color_image* in, uint32_t n_fra
                        const rship_color_cfg* cfg, const rship_color_image* out, uint64_t* n_outside, size_t budget_bytes) {
     DeviceGuard dev_guard(c);
     if (color_check(c, cfg)) return 1;
-    rship_stabilize_cfg L = cfg->luma;
-    if (!color_is_16(cfg->format)) L.fill = cfg->fill[0];
-    const uint32_t ow = L.out_width, oh = L.out_height;
+    const rship_stabilize_cfg L = color_luma(cfg);
     return color_frames_run(c, in, n_frames, frame_times, targets, cfg, out, n_outside, budget_bytes, true,
                             [&](const ColorLaunch& K, uint32_t, uint32_t cnt) {
-        const ColorArgs& A = K.A;
-        const dim3 grid((ow + kRectTW - 1) / kRectTW, (oh + kRectTH - 1) / kRectTH, cnt);
-        const dim3 grid_c((ow / 2 + kRectTW - 1) / kRectTW, (oh / 2 + kRectTH - 1) / kRectTH, cnt);
-        switch (cfg->format) {
-        case 0: stab_launch<false>(c, &L, K.G, cnt); break;
-        case 1: camfilt_launch<PickNv12>(c, L.camera, L.filter, grid_c, A); break;
-        case 2: camfilt_launch<PickI420>(c, L.camera, L.filter, grid_c, A); break;
-        case 3: camfilt_launch<PickRgba>(c, L.camera, L.filter, grid, A); break;
-        case 16: camfilt_launch<PickGray16>(c, L.camera, L.filter, grid, A, K.fill16_y); break;
-        case 17: camfilt_launch<PickP010>(c, L.camera, L.filter, grid_c, A, K.fill16_y, K.fill16_uv); break;
-        case 18: camfilt_launch<PickP016>(c, L.camera, L.filter, grid_c, A, K.fill16_y, K.fill16_uv); break;
-        case 19: camfilt_launch<PickI010>(c, L.camera, L.filter, grid_c, A, K.fill16_y, K.fill16_uv); break;
-        }
+        if (cfg->format == 0) stab_launch<false>(c, &L, K.G, cnt);
+        else format_launch<ColorFamily>(c, cfg->format, L.camera, L.filter, L.out_width, L.out_height, cnt, K);
     });
 }
 
@@ -4705,13 +4798,12 @@ int rship_color_map(rship_ctx* c, int plane, double frame_time, const double* ta
 
 namespace {
 
-template <int C, int F> struct PercamNv12 { static constexpr auto kernel = percam_yuv8_kernel<C, true, F>; };
-template <int C, int F> struct PercamI420 { static constexpr auto kernel = percam_yuv8_kernel<C, false, F>; };
-template <int C, int F> struct PercamRgba { static constexpr auto kernel = percam_rgba8_kernel<C, F>; };
-template <int C, int F> struct PercamGray16 { static constexpr auto kernel = percam_gray16_kernel<C, F>; };
-template <int C, int F> struct PercamP010 { static constexpr auto kernel = percam_yuv16_kernel<C, true, 6, F>; };
-template <int C, int F> struct PercamP016 { static constexpr auto kernel = percam_yuv16_kernel<C, true, 0, F>; };
-template <int C, int F> struct PercamI010 { static constexpr auto kernel = percam_yuv16_kernel<C, false, 0, F>; };
+struct PercamFamily : FamilyLaunch {
+    template <int C, bool NV, int F> static constexpr auto yuv8 = percam_yuv8_kernel<C, NV, F>;
+    template <int C, int F> static constexpr auto rgba8 = percam_rgba8_kernel<C, F>;
+    template <int C, int F> static constexpr auto gray16 = percam_gray16_kernel<C, F>;
+    template <int C, bool NV, int SH, int F> static constexpr auto yuv16 = percam_yuv16_kernel<C, NV, SH, F>;
+};
 
 } // namespace
 
@@ -4723,66 +4815,33 @@ int rship_colorzoom_frames(rship_ctx* c, const rship_color_image* in, uint32_t n
     DeviceGuard dev_guard(c);
     if (color_check(c, cfg)) return 1;
     if (!zooms) return set_err(c, "colorzoom: null pointer");
-    rship_stabilize_cfg L = cfg->luma;
-    if (!color_is_16(cfg->format)) L.fill = cfg->fill[0];
-    // the cameras of all frames, fp64 products as the colour front's configuration holds them for a constant zoom:
-    // luma (fx zoom, fy zoom), chroma the same times 0.5 (color_chroma_camera).  GRAY8: zoom_render_kernel's pairs
+    const rship_stabilize_cfg L = color_luma(cfg);
+    // the cameras of all frames: luma and chroma.  GRAY8: zoom_render_kernel's pairs
     const size_t per = cfg->format == 0 ? 2 : 4;
-    std::vector<double> cams((size_t)n_frames * per);
-    for (uint32_t f = 0; f < n_frames; ++f) {
-        if (!(zooms[f] > 0.0) || !std::isfinite(zooms[f])) return set_err(c, "colorzoom: every zoom must be finite and > 0");
-        double* k = &cams[per * (size_t)f];
-        k[0] = L.cam[0] * zooms[f];
-        k[1] = L.cam[1] * zooms[f];
-        if (per == 4) {
-            k[2] = k[0] * 0.5;
-            k[3] = k[1] * 0.5;
-        }
-    }
-    if (n_frames) {
-        if (ensure(c, c->stab_zooms, cams.size() * 8)) return 1;
-        RS_HIP(hipMemcpy(c->stab_zooms.p, cams.data(), cams.size() * 8, hipMemcpyHostToDevice));
-    }
-    const uint32_t ow = L.out_width, oh = L.out_height;
+    if (zoom_cams(c, &L, zooms, n_frames, per, "colorzoom: every zoom must be finite and > 0")) return 1;
+    ZoomRenderArgs Z = zoom_render_args(&L); // GRAY8
     PercamArgs P{};
-    P.cx = L.cam[2];
-    P.cy = L.cam[3];
+    P.cx = Z.cx;
+    P.cy = Z.cy;
     P.cx_c = cfg->chroma.cam[2];
     P.cy_c = cfg->chroma.cam[3];
-    P.k1 = L.lens[5];
-    P.k2 = L.lens[6];
-    P.k3 = L.lens[7];
-    P.k4 = L.lens[8];
-    ZoomRenderArgs Z{}; // GRAY8
-    Z.cx = P.cx;
-    Z.cy = P.cy;
-    Z.k1 = P.k1;
-    Z.k2 = P.k2;
-    Z.k3 = P.k3;
-    Z.k4 = P.k4;
+    P.k1 = Z.k1;
+    P.k2 = Z.k2;
+    P.k3 = Z.k3;
+    P.k4 = Z.k4;
     return color_frames_run(c, in, n_frames, frame_times, targets, cfg, out, n_outside, budget_bytes, false,
                             [&](const ColorLaunch& K, uint32_t f0, uint32_t cnt) {
-        const dim3 grid((ow + kRectTW - 1) / kRectTW, (oh + kRectTH - 1) / kRectTH, cnt);
-        const dim3 grid_c((ow / 2 + kRectTW - 1) / kRectTW, (oh / 2 + kRectTH - 1) / kRectTH, cnt);
         if (cfg->format == 0) {
             Z.S = K.G;
             Z.cams = (const double*)c->stab_zooms.p + 2 * (size_t)f0;
-            camfilt_launch<PickZoom>(c, L.camera, L.filter, grid, Z);
+            camfilt_launch<PickZoom>(c, L.camera, L.filter, stab_grid(&L, cnt), Z);
             return;
         }
         P.C = K.A;
         P.cams = (const double*)c->stab_zooms.p + 4 * (size_t)f0;
         P.fill_y = K.fill16_y;
         P.fill_uv = K.fill16_uv;
-        switch (cfg->format) {
-        case 1: camfilt_launch<PercamNv12>(c, L.camera, L.filter, grid_c, P); break;
-        case 2: camfilt_launch<PercamI420>(c, L.camera, L.filter, grid_c, P); break;
-        case 3: camfilt_launch<PercamRgba>(c, L.camera, L.filter, grid, P); break;
-        case 16: camfilt_launch<PercamGray16>(c, L.camera, L.filter, grid, P); break;
-        case 17: camfilt_launch<PercamP010>(c, L.camera, L.filter, grid_c, P); break;
-        case 18: camfilt_launch<PercamP016>(c, L.camera, L.filter, grid_c, P); break;
-        case 19: camfilt_launch<PercamI010>(c, L.camera, L.filter, grid_c, P); break;
-        }
+        format_launch<PercamFamily>(c, cfg->format, L.camera, L.filter, L.out_width, L.out_height, cnt, P);
     });
 }
 
@@ -4806,63 +4865,44 @@ int rship_infill_frames(rship_ctx* c, const uint8_t* frames, uint32_t n_frames, 
     DeviceGuard dev_guard(c);
     if (stab_check(c, cfg)) return 1;
     if (radius < 0 || radius > rs::kInfillMaxRadius) return set_err(c, "infill: radius must be 0 .. 8");
-    if (!frames || !out || !frame_times) return set_err(c, "stabilize: null pointer");
-    if (!n_frames) return 0;
-    const uint32_t w = cfg->width, h = cfg->height, ow = cfg->out_width, oh = cfg->out_height, r = (uint32_t)radius, places = 2 * r + 1;
-    if (pitch < w || out_pitch < ow || (n_frames > 1 && (frame_stride < pitch * h || out_stride < out_pitch * oh)))
-        return set_err(c, "stabilize: pitch or frame stride too small");
-    bool dev_in = false, dev_out = false;
-    if (rect_pointer(c, frames, "the frames", &dev_in, "stabilize") || rect_pointer(c, out, "the stabilised frames", &dev_out, "stabilize")) return 1;
-    // the chunk: per output frame its tables, its input and its output; per slot the halo's input frames besides
-    const rs::FramePlan P = gray_plan(n_frames, budget_bytes, places, r, w, h, dev_in, ow, oh, dev_out);
-    // (the counts: [0, n_frames) the filled pixels, [n_frames, 2 n_frames) the borrowed ones)
-    if (ensure(c, c->rect_times, (size_t)n_frames * 8) || ensure(c, c->rect_count, (size_t)n_frames * 16)) return 1;
-    RS_HIP(hipMemcpy(c->rect_times.p, frame_times, (size_t)n_frames * 8, hipMemcpyHostToDevice));
-    RS_HIP(hipMemsetAsync(c->rect_count.p, 0, (size_t)n_frames * 16, c->stream));
-    if (stab_fill_targets(c, cfg, targets, n_frames) || stab_rays(c, cfg)) return 1;
-    InfillRowsArgs R{};
-    R.table = (const double*)c->coef64.p;
-    R.times = (const double*)c->rect_times.p;
-    R.targets = (const double*)c->stab_targets.p;
-    R.start = cfg->start;
-    R.fs = cfg->fs;
-    R.ro = cfg->lens[0];
-    R.delay = cfg->delay;
-    R.n_knots = c->n_knots;
-    R.rows = h;
+    const uint32_t h = cfg->height, places = 2 * (uint32_t)radius + 1;
+    InfillRowsArgs R = rows_args<InfillRowsArgs>(c, cfg);
     R.n_frames = n_frames;
     R.radius = radius;
-    const StabArgs S = stab_args(c, cfg);
     InfillArgs A{};
-    A.rays = S.rays;
-    A.lens = S.lens;
-    A.cam = S.cam;
-    A.y_scale = S.y_scale;
-    A.width = w;
-    A.height = h;
-    A.out_width = ow;
-    A.out_height = oh;
-    A.iterations = S.iterations;
-    A.fill = S.fill;
-    A.n_frames = n_frames;
-    A.radius = radius;
-    // both counts in one download
+    // (the counts: [0, n_frames) the filled pixels, [n_frames, 2 n_frames) the borrowed ones; both in one download)
     std::vector<uint64_t> counts(n_outside || n_borrowed ? 2 * (size_t)n_frames : 0);
-    if (frame_pipeline(c, P, 1, gray_image(frames, pitch, frame_stride), gray_image(out, out_pitch, out_stride), counts.empty() ? nullptr : counts.data(),
-                       counts.size(), [&](const FrameChunk& K) -> int {
+    if (gray_frames_call(c, "stabilize", "the stabilised frames", gray_image(frames, pitch, frame_stride), cfg->width, h,
+                         gray_image(out, out_pitch, out_stride), cfg->out_width, cfg->out_height, n_frames, frame_times, budget_bytes,
+                         (uint32_t)radius, 2, counts.empty() ? nullptr : counts.data(), [&]() -> int {
+            if (stab_fill_targets(c, cfg, targets, n_frames) || stab_rays(c, cfg)) return 1;
+            R.times = (const double*)c->rect_times.p;
+            R.targets = (const double*)c->stab_targets.p;
+            const StabArgs S = stab_args(c, cfg);
+            A.rays = S.rays;
+            A.lens = S.lens;
+            A.cam = S.cam;
+            A.y_scale = S.y_scale;
+            A.width = S.width;
+            A.height = S.height;
+            A.out_width = S.out_width;
+            A.out_height = S.out_height;
+            A.iterations = S.iterations;
+            A.fill = S.fill;
+            A.n_frames = n_frames;
+            A.radius = radius;
+            return 0;
+        }, [&](const FrameChunk& K, bool dev_in) -> int {
             R.rows_tab = (float*)K.base;
             R.f0 = K.f0;
             hipLaunchKernelGGL(infill_rows_kernel, dim3((h + 1 + 255) / 256, places, K.cnt), dim3(256), 0, c->stream, R);
             RS_HIP(hipGetLastError());
-            A.rows_tab = (const float*)K.base;
-            A.outside = (unsigned long long*)c->rect_count.p + K.f0;
-            A.borrowed = (unsigned long long*)c->rect_count.p + n_frames + K.f0;
+            gray_chunk_args(c, A, K);
+            A.borrowed = A.outside + n_frames;
             A.f0 = K.f0;
             // (device frames: the kernel reads the neighbours in place, from frame 0 of the call)
-            A.src = dev_in ? frames : K.src[0];
+            if (dev_in) A.src = frames;
             A.src0 = dev_in ? 0 : K.src0;
-            A.src_pitch = K.src_pitch[0]; A.src_stride = K.src_stride[0];
-            A.dst = K.dst[0]; A.dst_pitch = K.dst_pitch[0]; A.dst_stride = K.dst_stride[0];
             camfilt_launch<PickInfill>(c, cfg->camera, cfg->filter, stab_grid(cfg, K.cnt), A);
             RS_HIP(hipGetLastError());
             return 0;
@@ -4881,13 +4921,12 @@ int rship_infill_frames(rship_ctx* c, const uint8_t* frames, uint32_t n_frames, 
 // and region, and a halo of `radius` input frames on each side of a chunk, per plane.
 
 namespace {
-template <int C, int F> struct DonorNv12 { static constexpr auto kernel = donor_yuv8_kernel<C, true, F>; };
-template <int C, int F> struct DonorI420 { static constexpr auto kernel = donor_yuv8_kernel<C, false, F>; };
-template <int C, int F> struct DonorRgba { static constexpr auto kernel = donor_rgba8_kernel<C, F>; };
-template <int C, int F> struct DonorGray16 { static constexpr auto kernel = donor_gray16_kernel<C, F>; };
-template <int C, int F> struct DonorP010 { static constexpr auto kernel = donor_yuv16_kernel<C, true, 6, F>; };
-template <int C, int F> struct DonorP016 { static constexpr auto kernel = donor_yuv16_kernel<C, true, 0, F>; };
-template <int C, int F> struct DonorI010 { static constexpr auto kernel = donor_yuv16_kernel<C, false, 0, F>; };
+struct DonorFamily : FamilyLaunch {
+    template <int C, bool NV, int F> static constexpr auto yuv8 = donor_yuv8_kernel<C, NV, F>;
+    template <int C, int F> static constexpr auto rgba8 = donor_rgba8_kernel<C, F>;
+    template <int C, int F> static constexpr auto gray16 = donor_gray16_kernel<C, F>;
+    template <int C, bool NV, int SH, int F> static constexpr auto yuv16 = donor_yuv16_kernel<C, NV, SH, F>;
+};
 } // namespace
 
 extern "C" {
@@ -4900,8 +4939,7 @@ int rship_colorinfill_frames(rship_ctx* c, const rship_color_image* in, uint32_t
     if (radius < 0 || radius > rs::kInfillMaxRadius) return set_err(c, "colorinfill: radius must be 0 .. 8");
     if (!in || !out || !frame_times) return set_err(c, "color: null pointer");
     if (!n_frames) return 0;
-    rship_stabilize_cfg L = cfg->luma;
-    if (!color_is_16(cfg->format)) L.fill = cfg->fill[0];
+    const rship_stabilize_cfg L = color_luma(cfg);
     if (cfg->format == 0) {
         // GRAY8: the gray infill's kernels; its counts go to the caller in pairs, the chroma entries 0
         if (!in->plane[0] || !out->plane[0]) return set_err(c, "color: null pointer");
@@ -4915,91 +4953,36 @@ int rship_colorinfill_frames(rship_ctx* c, const rship_color_image* in, uint32_t
         }
         return 0;
     }
-    const bool yuv = color_is_yuv(cfg->format);
-    const uint32_t h = L.height, hc = yuv ? h / 2 : 0, ow = L.out_width, oh = L.out_height, places = 2 * (uint32_t)radius + 1;
-    rs::FrameLayout q;
-    int np = 0;
-    bool dev_in = false;
-    if (color_layout(c, in, n_frames, cfg, out, budget_bytes, &q, &np, &dev_in)) return 1;
-    // the chunk: per output frame its tables of both regions, its input and its output planes; per slot the halo's input
-    // frames besides
-    q.tabs = places;
-    q.radius = (uint32_t)radius;
-    const rs::FramePlan P = rs::plan_frames(q);
-    // the frames' times, then the chroma planes'; the counts: filled plane 0, filled chroma, borrowed plane 0, borrowed chroma
-    if (ensure(c, c->rect_times, (size_t)n_frames * 16) || ensure(c, c->rect_count, (size_t)n_frames * 32)) return 1;
-    std::vector<double> times(2 * (size_t)n_frames);
-    for (uint32_t k = 0; k < n_frames; ++k) {
-        times[k] = frame_times[k];
-        times[n_frames + k] = frame_times[k] + cfg->chroma_time;
-    }
-    RS_HIP(hipMemcpy(c->rect_times.p, times.data(), times.size() * 8, hipMemcpyHostToDevice));
-    RS_HIP(hipMemsetAsync(c->rect_count.p, 0, (size_t)n_frames * 32, c->stream));
-    if (stab_fill_targets(c, &L, targets, n_frames) || stab_rays(c, &L) || (yuv && stab_rays(c, &cfg->chroma, true))) return 1;
-    DonorRowsArgs R{};
-    R.table = (const double*)c->coef64.p;
-    R.times = (const double*)c->rect_times.p;
-    R.times_c = (const double*)c->rect_times.p + n_frames;
-    R.targets = (const double*)c->stab_targets.p;
-    R.start = L.start;
-    R.fs = L.fs;
-    R.ro = L.lens[0];
-    R.delay = L.delay;
-    R.n_knots = c->n_knots;
-    R.rows = h;
-    R.rows_c = hc;
-    R.n_frames = n_frames;
-    R.radius = radius;
-    const ColorLaunch K = color_launch(c, cfg, L);
+    rs::FramePlane planes[3];
+    const int np = color_planes(cfg->format, L.width, L.height, planes);
     DonorArgs D{};
-    D.C = K.A;
-    D.fill_y = K.fill16_y;
-    D.fill_uv = K.fill16_uv;
     D.n_frames = n_frames;
     D.radius = radius;
-    ColorArgs& A = D.C;
-    unsigned long long* count = (unsigned long long*)c->rect_count.p;
-    // all four counts in one download
-    std::vector<uint64_t> counts(n_outside || n_borrowed ? 4 * (size_t)n_frames : 0);
-    if (frame_pipeline(c, P, np, *in, *out, counts.empty() ? nullptr : counts.data(), counts.size(), [&](const FrameChunk& C) -> int {
-            R.rows_tab = (float*)(C.base + P.off_tab[0]);
-            R.rows_tab_c = (float*)(C.base + P.off_tab[1]);
-            R.f0 = C.f0;
-            hipLaunchKernelGGL(donor_rows_kernel, dim3((h + 1 + (yuv ? hc + 1 : 0) + 255) / 256, places, C.cnt), dim3(256), 0, c->stream, R);
-            RS_HIP(hipGetLastError());
-            A.luma.rows_tab = R.rows_tab;
-            A.chroma.rows_tab = R.rows_tab_c;
-            A.outside = count + C.f0;
-            A.outside_c = count + n_frames + C.f0;
-            D.borrowed = count + 2 * (size_t)n_frames + C.f0;
-            D.borrowed_c = count + 3 * (size_t)n_frames + C.f0;
-            D.f0 = C.f0;
-            // (device frames: the kernels read the neighbours in place, from frame 0 of the call)
-            D.src0 = dev_in ? 0 : C.src0;
-            for (int k = 0; k < np; ++k) {
-                A.src[k] = dev_in ? in->plane[k] : C.src[k]; A.src_pitch[k] = C.src_pitch[k]; A.src_stride[k] = C.src_stride[k];
-                A.dst[k] = C.dst[k]; A.dst_pitch[k] = C.dst_pitch[k]; A.dst_stride[k] = C.dst_stride[k];
-            }
-            const dim3 grid((ow + kRectTW - 1) / kRectTW, (oh + kRectTH - 1) / kRectTH, C.cnt);
-            const dim3 grid_c((ow / 2 + kRectTW - 1) / kRectTW, (oh / 2 + kRectTH - 1) / kRectTH, C.cnt);
-            switch (cfg->format) {
-            case 1: camfilt_launch<DonorNv12>(c, L.camera, L.filter, grid_c, D); break;
-            case 2: camfilt_launch<DonorI420>(c, L.camera, L.filter, grid_c, D); break;
-            case 3: camfilt_launch<DonorRgba>(c, L.camera, L.filter, grid, D); break;
-            case 16: camfilt_launch<DonorGray16>(c, L.camera, L.filter, grid, D); break;
-            case 17: camfilt_launch<DonorP010>(c, L.camera, L.filter, grid_c, D); break;
-            case 18: camfilt_launch<DonorP016>(c, L.camera, L.filter, grid_c, D); break;
-            case 19: camfilt_launch<DonorI010>(c, L.camera, L.filter, grid_c, D); break;
-            }
-            RS_HIP(hipGetLastError());
-            return 0;
-        }))
-        return 1;
-    for (size_t k = 0; k < counts.size() / 4; ++k) {
-        if (n_outside) { n_outside[2 * k] = counts[k]; n_outside[2 * k + 1] = counts[n_frames + k]; }
-        if (n_borrowed) { n_borrowed[2 * k] = counts[2 * (size_t)n_frames + k]; n_borrowed[2 * k + 1] = counts[3 * (size_t)n_frames + k]; }
-    }
-    return 0;
+    // (the counts: filled plane 0, filled chroma, borrowed plane 0, borrowed chroma)
+    uint64_t* const pairs[2] = {n_outside, n_borrowed};
+    return color_call<DonorRowsArgs>(c, in, n_frames, frame_times, targets, cfg, out, budget_bytes, (uint32_t)radius, true, pairs, 2,
+                                     [&](const FrameChunk& C, DonorRowsArgs& R, ColorLaunch& K, bool dev_in) -> int {
+        R.times = (const double*)c->rect_times.p;
+        R.times_c = R.times + n_frames;
+        R.targets = (const double*)c->stab_targets.p;
+        R.f0 = C.f0;
+        R.n_frames = n_frames;
+        R.radius = radius;
+        hipLaunchKernelGGL(donor_rows_kernel, dim3(color_rows_blocks(R.rows, R.rows_c), 2 * (uint32_t)radius + 1, C.cnt), dim3(256), 0, c->stream, R);
+        RS_HIP(hipGetLastError());
+        D.C = K.A;
+        D.fill_y = K.fill16_y;
+        D.fill_uv = K.fill16_uv;
+        D.borrowed = D.C.outside + 2 * (size_t)n_frames;
+        D.borrowed_c = D.C.outside + 3 * (size_t)n_frames;
+        D.f0 = C.f0;
+        // (device frames: the kernels read the neighbours in place, from frame 0 of the call)
+        D.src0 = dev_in ? 0 : C.src0;
+        for (int k = 0; dev_in && k < np; ++k) D.C.src[k] = in->plane[k];
+        format_launch<DonorFamily>(c, cfg->format, L.camera, L.filter, L.out_width, L.out_height, C.cnt, D);
+        RS_HIP(hipGetLastError());
+        return 0;
+    });
 }
 
 } // extern "C"

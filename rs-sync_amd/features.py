@@ -14,7 +14,7 @@ from collections import namedtuple
 import numpy as np
 
 from . import track
-from .problem import RsSyncError
+from .problem import RsSyncError, product_library
 
 _PD = C.POINTER(C.c_double)
 _SZ = C.c_size_t
@@ -52,20 +52,11 @@ STATUS = {**track.STATUS, 4: "forward-backward mismatch"}
 # per pair k, the first counts[k] entries of each array are set
 Features = namedtuple("Features", "counts points_a points_b status fb_error")
 
-_BOUND = None
-
 
 def library():
     """the product library with the feature tracker's signatures attached"""
-    global _BOUND
-    lib = track.library()
-    if _BOUND is not lib:
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        _BOUND = lib
-    return lib
+    track.library()
+    return product_library(SIGNATURES)
 
 
 def _lib_of(problem):

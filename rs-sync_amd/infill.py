@@ -14,9 +14,10 @@ import ctypes as C
 
 import numpy as np
 
-from .problem import RsSyncError, load_library
+from .problem import RsSyncError, product_library, product_only
 from .rectify import _check, _lens, _out_like, _out_view
-from .stabilize import (CAMERA_LENS, DEFAULT_ITERATIONS, FILTER_BILINEAR, StabilizeParams, _Cfg, _targets, _times, params)
+from .stabilize import (CAMERA_LENS, DEFAULT_ITERATIONS, FILTER_BILINEAR, StabilizeParams, _Cfg, _launcher_cfg, _targets, _times,
+                        params)
 from .track import _frames
 
 _PD = C.POINTER(C.c_double)
@@ -33,27 +34,14 @@ SIGNATURES = {
     "rship_last_error": (C.c_char_p, [C.c_void_p]),
 }
 
-_BOUND = None
-
 
 def library():
     """the product library with the infill's signatures attached"""
-    global _BOUND
-    lib = load_library()
-    if _BOUND is not lib:
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        _BOUND = lib
-    return lib
+    return product_library(SIGNATURES)
 
 
 def _lib_of(problem):
-    lib = library()
-    if problem._lib is not lib:
-        raise RsSyncError("the infill runs in the product library only")
-    return lib
+    return product_only(problem, library(), "the infill")
 
 
 def candidates(f, n_frames, radius):
@@ -96,11 +84,7 @@ def stabilize_frames_infilled_budget(problem, frames, frame_times, lens, delay, 
     t = _times(frame_times, n)
     L = _lens(lens)
     ow, oh = (w, h) if out_size is None else (int(out_size[0]), int(out_size[1]))
-    fs, start, n_knots = problem.gyro_info()
-    sx, sy = ow / w, oh / h
-    cam = (C.c_double * 4)(L[1] * sx * float(zoom), L[2] * sy * float(zoom), L[3] * sx, L[4] * sy)
-    cfg = _Cfg(w, h, ow, oh, (C.c_double * 9)(*L), cam, start, fs, n_knots, float(delay), float(sigma), int(camera), int(iterations),
-               int(fill), int(filter))
+    cfg = _launcher_cfg(problem, w, h, ow, oh, L, delay, sigma, camera, iterations, fill, filter, zoom=zoom)
     if targets is not None:             # (rs::limit_unit's operations in its order: the launcher takes unit quaternions)
         q = np.array(targets, np.float64)
         targets = q / np.sqrt(((q[:, 0] * q[:, 0] + q[:, 1] * q[:, 1]) + q[:, 2] * q[:, 2]) + q[:, 3] * q[:, 3])[:, None]

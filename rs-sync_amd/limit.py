@@ -17,7 +17,7 @@ import ctypes as C
 
 import numpy as np
 
-from .problem import RsSyncError, load_library
+from .problem import RsSyncError, product_library, product_only
 from .rectify import _check, _lens
 from .stabilize import StabilizeParams, _targets, _times, params, stabilize_coverage
 
@@ -36,27 +36,14 @@ SIGNATURES = {
     "rssync_limit_targets": (C.c_int, [C.c_void_p, _PD, _SZ, C.c_double, C.c_double, _PD, C.c_double, _PD, _PD]),
 }
 
-_BOUND = None
-
 
 def library():
     """the product library with the limiter's signatures attached"""
-    global _BOUND
-    lib = load_library()
-    if _BOUND is not lib:
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        _BOUND = lib
-    return lib
+    return product_library(SIGNATURES)
 
 
 def _lib_of(problem):
-    lib = library()
-    if problem._lib is not lib:
-        raise RsSyncError("the path limiter runs in the product library only")
-    return lib
+    return product_only(problem, library(), "the path limiter")
 
 
 def _per_frame(values, n, what):

@@ -121,9 +121,9 @@ SIGNATURES = {
 }
 
 
-def bind(lib):
-    """Attach the C-ABI signatures of include/rssync_c.h to a loaded library."""
-    for name, (res, args) in SIGNATURES.items():
+def bind(lib, signatures=SIGNATURES):
+    """Attach a table of C-ABI signatures (include/rssync_c.h's, or a front door's own) to a loaded library."""
+    for name, (res, args) in signatures.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -142,6 +142,25 @@ def load_library():
             "(make -C rs-sync_amd/csrc); there is no fallback implementation")
     _LIB = bind(C.CDLL(path))
     return _LIB
+
+
+_ATTACHED = {}      # id of a front door's signature table -> the library it was attached to
+
+
+def product_library(signatures):
+    """The product library with a front door's signature table attached, once per loaded library (a missing symbol raises)."""
+    lib = load_library()
+    if _ATTACHED.get(id(signatures)) is not lib:
+        bind(lib, signatures)
+        _ATTACHED[id(signatures)] = lib
+    return lib
+
+
+def product_only(problem, lib, who):
+    """-> lib, the product library, for a call of front door `who` on `problem`: the front doors have no CPU test double."""
+    if problem._lib is not lib:
+        raise RsSyncError("%s runs in the product library only" % who)
+    return lib
 
 
 def _d(a):

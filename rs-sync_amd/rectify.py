@@ -14,7 +14,7 @@ import ctypes as C
 
 import numpy as np
 
-from .problem import RsSyncError, load_library
+from .problem import RsSyncError, product_library, product_only
 from .track import _frames
 
 _PD = C.POINTER(C.c_double)
@@ -49,20 +49,10 @@ SIGNATURES = {
 
 DEFAULT_ITERATIONS = 3
 
-_BOUND = None
-
 
 def library():
     """the product library with the rectifier's signatures attached"""
-    global _BOUND
-    lib = load_library()
-    if _BOUND is not lib:
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        _BOUND = lib
-    return lib
+    return product_library(SIGNATURES)
 
 
 def params(ref_row=None, iterations=DEFAULT_ITERATIONS, fill=0):
@@ -83,10 +73,7 @@ def _check(problem, rc):
 
 
 def _lib_of(problem):
-    lib = library()
-    if problem._lib is not lib:
-        raise RsSyncError("the rectifier runs in the product library only")
-    return lib
+    return product_only(problem, library(), "the rectifier")
 
 
 def _is_torch(x):

@@ -17,7 +17,7 @@ import ctypes as C
 
 import numpy as np
 
-from .problem import RsSyncError, load_library
+from .problem import RsSyncError, product_library, product_only
 from .rectify import _check, _is_torch, _lens, _out_like, _out_view
 from .track import _frames
 
@@ -59,27 +59,14 @@ SIGNATURES = {
     "rship_last_error": (C.c_char_p, [C.c_void_p]),
 }
 
-_BOUND = None
-
 
 def library():
     """the product library with the stabiliser's signatures attached"""
-    global _BOUND
-    lib = load_library()
-    if _BOUND is not lib:
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        _BOUND = lib
-    return lib
+    return product_library(SIGNATURES)
 
 
 def _lib_of(problem):
-    lib = library()
-    if problem._lib is not lib:
-        raise RsSyncError("the stabiliser runs in the product library only")
-    return lib
+    return product_only(problem, library(), "the stabiliser")
 
 
 def params(sigma=0.0, zoom=1.0, camera=CAMERA_LENS, out_camera=None, iterations=DEFAULT_ITERATIONS, fill=0, filter=FILTER_BILINEAR):
@@ -104,6 +91,17 @@ def _times(frame_times, n=None):
     if t.ndim != 1 or (n is not None and t.shape != (n,)):
         raise ValueError("frame_times must hold one time per frame")
     return t
+
+
+def _launcher_cfg(problem, w, h, ow, oh, lens, delay, sigma, camera, iterations, fill, filter, zoom=1.0, cam=None):
+    """rship_stabilize_cfg for the *_budget calls of the internal launchers.  cam: None = the lens's camera scaled to the
+    output, its focal lengths times `zoom` (1: a launcher that multiplies by a zoom per frame itself)"""
+    fs, start, n_knots = problem.gyro_info()
+    if cam is None:
+        sx, sy = ow / w, oh / h
+        cam = (lens[1] * sx * float(zoom), lens[2] * sy * float(zoom), lens[3] * sx, lens[4] * sy)
+    return _Cfg(w, h, ow, oh, (C.c_double * 9)(*lens), (C.c_double * 4)(*cam), start, fs, n_knots, float(delay), float(sigma), int(camera),
+                int(iterations), int(fill), int(filter))
 
 
 def stabilize_path(problem, frame_times, ro, delay, sigma, out=None):
@@ -200,11 +198,7 @@ def stabilize_frames_budget(problem, frames, frame_times, lens, delay, budget_by
     t = _times(frame_times, n)
     L = _lens(lens)
     ow, oh = (w, h) if out_size is None else (int(out_size[0]), int(out_size[1]))
-    fs, start, n_knots = problem.gyro_info()
-    sx, sy = ow / w, oh / h
-    cam = (C.c_double * 4)(L[1] * sx, L[2] * sy, L[3] * sx, L[4] * sy)
-    cfg = _Cfg(w, h, ow, oh, (C.c_double * 9)(*L), cam, start, fs, n_knots, float(delay), float(sigma), CAMERA_LENS,
-               int(iterations), int(fill), int(filter))
+    cfg = _launcher_cfg(problem, w, h, ow, oh, L, delay, sigma, CAMERA_LENS, iterations, fill, filter)
     out = np.empty((n, oh, ow), np.uint8)
     outside = np.zeros(max(n, 1), np.uint64)
     ctx = C.c_void_p(problem.device_context())

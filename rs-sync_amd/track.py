@@ -14,7 +14,7 @@ import ctypes as C
 
 import numpy as np
 
-from .problem import RsSyncError, load_library
+from .problem import RsSyncError, product_library, product_only
 
 _PD = C.POINTER(C.c_double)
 
@@ -45,20 +45,10 @@ SIGNATURES = {
 DEFAULTS = dict(grid_step=200, window=21, levels=4, max_iters=30, epsilon=0.01, min_eig=1e-4)
 STATUS = {0: "ok", 1: "ill-conditioned", 2: "left the image", 3: "iteration cap"}
 
-_BOUND = None
-
 
 def library():
     """the product library with the tracker's signatures attached"""
-    global _BOUND
-    lib = load_library()
-    if _BOUND is not lib:
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        _BOUND = lib
-    return lib
+    return product_library(SIGNATURES)
 
 
 def grid(width, height, step=200):
@@ -108,10 +98,7 @@ def _check(problem, rc):
 
 
 def _lib_of(problem):
-    lib = library()
-    if problem._lib is not lib:
-        raise RsSyncError("the tracker runs in the product library only")
-    return lib
+    return product_only(problem, library(), "the tracker")
 
 
 def track_points(problem, frames, grid_step=200, **kw):
