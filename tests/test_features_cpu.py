@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import feature_cases as fc
 import feature_reference as fr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -147,6 +148,139 @@ def test_detect_threshold_and_cell_winner():
     faint = max(R[y, x] for y, x in np.argwhere(lm) if x >= 48)
     assert faint >= T and len(got) == 2                   # the faint square passes at quality 0.01 ...
     assert faint < fr.threshold(R, 0.5) and len(fr.detect(img, cell=48, block=5, quality=0.5)) == 1   # ... not at 0.5
+
+
+# --- the inputs of tests/test_gpu_feature_ties.py (tests/feature_cases.py) are not vacuous: by the numpy restatement alone
+# they hold the ties, slivers, non-positive cells and list lengths that the device tests are there for
+
+
+@pytest.mark.parametrize("h,w,P,seed", fc.TIE_FRAMES)
+def test_tie_frames_hold_ties_in_every_configuration(h, w, P, seed):
+    """Every (frame, configuration) of the device's tie test has pixels that tie with a neighbour for the local maximum
+    (plateau) and pixels that only the tie rule rejects (dropped_by_tie); every frame has, at each cell size, cells whose
+    winner is decided by the raster index alone.  kaleidoscope(197, 331, 13, 197): 2524 plateau pixels, 1262 dropped and
+    170 tied cells at (16, 3, 1e-3); 18 of 18 cells tied at (64, 9, 0.01); 6 of 6 at (128, 5, 0.5); 84 features at
+    (16, 9, 1.0)."""
+    img = fc.kaleidoscope(h, w, P, seed)
+    tied = {16: 0, 64: 0, 128: 0}
+    for cell, block, quality in fc.TIE_CONFIGS:
+        s = fc.tie_stats(img, cell, block, quality)
+        print((h, w, P, seed), (cell, block, quality), s)
+        assert s["plateau"] > 0 and s["dropped_by_tie"] > 0, ((cell, block, quality), s)
+        assert s["kept"] > 0
+        tied[cell] += s["cells_with_tied_best"]
+    assert all(n > 0 for n in tied.values()), tied
+
+
+def test_tie_frames_reach_every_stage_of_the_cell_reduction():
+    """Over the case list, tied bests of one cell meet in one thread (corner_beats in the row loop), in two lanes of one
+    wave (the shuffle butterfly) and in two waves (the reduction through LDS); see feature_cases.tie_paths.  Every frame
+    reaches the last two on its own."""
+    total = dict(thread=0, wave=0, workgroup=0)
+    for h, w, P, seed in fc.TIE_FRAMES:
+        img = fc.kaleidoscope(h, w, P, seed)
+        mine = dict(thread=0, wave=0, workgroup=0)
+        for cfg in fc.TIE_CONFIGS:
+            for k, v in fc.tie_paths(img, *cfg).items():
+                mine[k] += v
+        print((h, w, P, seed), mine)
+        assert mine["wave"] > 0 and mine["workgroup"] > 0, ((h, w), mine)
+        for k in total:
+            total[k] += mine[k]
+    assert all(v >= 2 for v in total.values()), total
+
+
+def test_quality_one_keeps_only_ties_for_the_maximum():
+    """quality = 1.0: T = R_max.  On the periodic frames more than one cell holds a pixel of that response, and nothing
+    else is listed (84 features on the 197 x 331 frame at cell 16, block 9)"""
+    for h, w, P, seed in fc.TIE_FRAMES:
+        img = fc.kaleidoscope(h, w, P, seed)
+        for cell, block, quality in fc.TIE_CONFIGS:
+            if quality != 1.0 or (cell >= h and cell >= w):
+                continue
+            R = fr.response(img, block)
+            pts = fc.detect(img, cell, block, 1.0)
+            assert fr.threshold(R, 1.0) == R.max()
+            assert len(pts) >= 2 and (R[pts[:, 1], pts[:, 0]] == R.max()).all(), ((h, w), cell, block, len(pts))
+
+
+def test_full_range_frame_stays_inside_the_number_formats():
+    """The 0/255 kaleidoscope: the tensor sums fit int32 (the assert in fr.response), R_max < 2^53 so that the fp64
+    threshold is exact, and block 9 reaches above 2^48 (508899560473125; 98 features at quality 1.0, cell 16).  The
+    smallest quality gives T = 1."""
+    img = fc.range_frame()
+    assert set(np.unique(img)) == {0, 255}
+    for block in fc.RANGE_BLOCKS:
+        R = fr.response(img, block)                          # (asserts the int32 bound itself)
+        r_max = int(R.max())
+        print("block %d: r_max %d = 2^%.2f" % (block, r_max, np.log2(r_max)))
+        assert 2 ** 43 < r_max < 2 ** 53
+        assert float(r_max) == r_max
+        assert fr.threshold(R, 1e-18) == 1 and fr.threshold(R, 1.0) == r_max
+        for cell in fc.RANGE_CELLS:
+            n = [len(fc.detect(img, cell, block, q)) for q in fc.RANGE_QUALITIES]
+            assert 2 <= n[0] <= n[1] <= n[2] <= n[3], (block, cell, n)
+    assert int(fr.response(img, 9).max()) > 2 ** 48
+
+
+@pytest.mark.parametrize("block", fc.SLIVER_BLOCKS)
+@pytest.mark.parametrize("cell", fc.SLIVER_CELLS)
+def test_sliver_cells_are_empty_up_to_b_and_hold_one_line_at_b_plus_one(cell, block):
+    """A last column and row of cells e px wide: no valid pixel, so no feature, at e = 1 and e = b = block // 2 + 1; one
+    valid column (row) at e = b + 1, on which the reference lists at least one feature ((19, 35) at cell 16, block 3: 1
+    in the last column of cells, 2 in the last row; (22, 38) at block 9: 1 and 2)"""
+    b = block // 2 + 1
+    for h, w, what in fc.sliver_sizes(cell, block):
+        img = fc.sliver_frame(h, w)
+        R = fr.response(img, block)
+        n = fc.cell_counts(fc.detect(img, cell, block, fc.SLIVER_QUALITY), h, w, cell)
+        last_col, last_row = int(n[-1].sum()), int(n[:, -1].sum())
+        print(cell, block, (h, w), what, "last column %d, last row %d of %d" % (last_col, last_row, n.sum()))
+        valid_col = (R[:, w // cell * cell:] != fr.NO_RESPONSE).any(axis=0).sum() if w % cell else None
+        valid_row = (R[h // cell * cell:] != fr.NO_RESPONSE).any(axis=1).sum() if h % cell else None
+        if what == "e=%d" % (b + 1):
+            assert valid_col == 1 and valid_row == 1
+            assert last_col >= 1 and last_row >= 1
+        else:
+            if w % cell:
+                assert valid_col == 0 and last_col == 0
+            if h % cell:
+                assert valid_row == 0 and last_row == 0
+        assert n.sum() >= 2                                  # (the full cells are not empty)
+
+
+def test_patch_frame_has_cells_without_a_positive_response():
+    """The textured frame with a constant rectangle and a ramp: thousands of valid pixels with R = 0 (5220) and with
+    R < 0, some cells without a feature (112 of 140 kept at either quality), none of them strictly inside the rectangle"""
+    img = fc.patch_frame()
+    R = fr.response(img, fc.PATCH_BLOCK)
+    v = R != fr.NO_RESPONSE
+    print("R = 0: %d, R < 0: %d" % ((R[v] == 0).sum(), (R[v] < 0).sum()))
+    assert (R[v] == 0).sum() >= 1000 and (R[v] < 0).sum() >= 1000
+    y0, y1, x0, x1 = fc.PATCH_FLAT
+    m = fc.PATCH_BLOCK // 2 + 1
+    assert (R[y0 + m:y1 - m, x0 + m:x1 - m] == 0).all()
+    y0, y1, x0, x1 = fc.PATCH_RAMP
+    assert (R[y0 + m:y1 - m, x0 + m:x1 - m] < 0).all()
+    cells = (-(-img.shape[0] // fc.PATCH_CELL)) * (-(-img.shape[1] // fc.PATCH_CELL))
+    for q in fc.PATCH_QUALITIES:
+        n = len(fc.detect(img, fc.PATCH_CELL, fc.PATCH_BLOCK, q))
+        assert cells // 2 < n < cells - 10, (q, n, cells)
+
+
+def test_round_frames_keep_every_cell():
+    """255, 256 and 272 cells, each with a feature: the select kernel's list crosses its 256-thread round in full"""
+    want = []
+    for h, w in fc.ROUND_FRAMES:
+        n = len(fc.detect(fc.round_frame(h, w), fc.ROUND_CELL, fc.ROUND_BLOCK, fc.ROUND_QUALITY))
+        assert n == (h // fc.ROUND_CELL) * (w // fc.ROUND_CELL), (h, w, n)
+        want.append(n)
+    assert want == [255, 256, 272]
+
+
+def test_mixed_batch_has_an_empty_frame_between_full_ones():
+    n = [len(fc.detect(f, *fc.MIXED_CONFIG)) for f in fc.mixed_frames()]
+    assert n[1] == 0 and n[0] == n[2] > 100 and n[3] > 100, n
 
 
 # sha256 of render(make_gyro(1.0, 1.0 + 6 / FPS, seed=5), 30, 33, quarter-resolution lens, 190 x 338, seed=5): frames,
