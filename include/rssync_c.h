@@ -289,6 +289,23 @@ int rssync_ext_readout_sweep(rssync_problem* p, const double* readouts, int n, d
 /* Give every pixel frame the readout ro (finite, >= 0), exactly as setting it again with lens.ro = ro would; frames set
  * by rssync_set_track_result are not touched. */
 int rssync_ext_set_readout(rssync_problem* p, double ro);
+/* The lens sweep: the same for the whole lens, for a clip without a calibration profile -- PreSync's cost has a minimum
+ * over the focal length, the distortion terms and (weakly) the principal point, while its delay barely moves.  For each
+ * lenses[i]: every frame of [frame_begin, frame_end) as if set again by rssync_ext_set_track_pixels with lenses[i] (its ro
+ * included), then PreSync(initial_delay, frame_begin, frame_end, search_step, search_radius) -> costs[i], delays[i] (bit
+ * for bit that loop; lenses that differ only in ro give rssync_ext_readout_sweep's arrays).  The frames keep their own
+ * lenses afterwards.  One pipeline on the device: the packed streams are rewritten from the pixels the device kept
+ * between the sweeps, one wait, one exchange between ranks.
+ * Errors, before anything is touched and naming the candidate: a frame of the range set by rssync_set_track_result (it
+ * has no pixels), a lens with non-finite entries, fx or fy not positive or a negative ro, n < 1.  A lens that turns rays
+ * non-finite fails the call after its one wait ("lens sweep: lens i: non-finite numbers in rays (...)"), as the loop would
+ * have failed at that candidate; the frames keep their own lenses then, too. */
+int rssync_ext_lens_sweep(rssync_problem* p, const rssync_lens* lenses, int n, double initial_delay,
+                          int64_t frame_begin, int64_t frame_end, double search_step, double search_radius,
+                          double* costs, double* delays);
+/* Give every pixel frame this lens (finite, fx and fy positive, ro >= 0), exactly as setting it again with it would;
+ * frames set by rssync_set_track_result are not touched. */
+int rssync_ext_set_lens(rssync_problem* p, const rssync_lens* lens);
 /* the packed device ray streams of one frame ({ax,bx,ay,by} and {az,bz,ta,tb} per pair), for tests */
 int rssync_ext_frame_rays(rssync_problem* p, int64_t frame, float* a4, float* b4, size_t cap, size_t* n);
 

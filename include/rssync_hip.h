@@ -72,7 +72,8 @@ typedef struct rship_frame {
 #define RSHIP_K_GYRO 6   /* gyro pipeline: integration scan, resampling, spline solve */
 #define RSHIP_K_LOSS_GRAD 7 /* residual + robust loss + analytic d/d-delay (one delay per window) */
 #define RSHIP_K_RETIME 8 /* re-timing kernel: a new readout for the pixel frames (rship_retime_pixels) */
-#define RSHIP_K_COUNT 9
+#define RSHIP_K_RELENS 9 /* re-lens kernel: a new lens for the pixel frames (rship_relens_pixels) */
+#define RSHIP_K_COUNT 10
 
 int rship_create(rship_ctx** out, int device /* -1 = current device */);
 void rship_destroy(rship_ctx* c);
@@ -195,6 +196,19 @@ int rship_pack_frames(rship_ctx* c, const rship_frame* table, const rship_pack_f
  * arrays may be reused at once); the selection, size classes and plan of the sums are left as they are, so that a batch of
  * sweeps can re-time between two of its sweeps.  Several devices: call rship_set_problem_frames again afterwards. */
 int rship_retime_pixels(rship_ctx* c, const rship_frame* table, const double* ro, uint32_t n_frames);
+
+/* A new LENS for the PIXEL frames without repacking them (the lens sweep, rssync_c.h: rssync_ext_lens_sweep,
+ * rssync_ext_set_lens).  table = as for rship_retime_pixels (a frame's record depends on its lens through the readout
+ * only); lenses[9 * i ..] = ro, fx, fy, cx, cy, k1 .. k4 of frame i (ignored for frames set as rays).  The re-lens kernel
+ * rewrites ALL packed streams of the pixel frames -- fp32 and fp64 directions and ta / tb -- from the raw pixel records:
+ * the bits rship_pack_frames gives with those lenses.  Asynchronous and in stream order, selection, size classes and plan
+ * stay, as for rship_retime_pixels.  Rays with a non-finite packed value are COUNTED (rship_pack_frames' *bad) into counter
+ * bad_slot of n_bad_slots (1 .. 8192); a call with bad_slot 0 opens that many counters and clears them, later calls name
+ * slots of the same set.  The counters are fetched by the wait of rship_presync_batch_collect, or by rship_relens_counts
+ * (out[0 .. n)), which waits for the stream itself where no such wait has covered the last launch. */
+int rship_relens_pixels(rship_ctx* c, const rship_frame* table, const double* lenses, uint32_t n_frames, uint32_t bad_slot,
+                        uint32_t n_bad_slots);
+int rship_relens_counts(rship_ctx* c, uint32_t n, uint32_t* out);
 
 /* One object over several devices (optional): the frame-table records of ALL frames of the problem (only n_rays, tmin,
  * tmax, range_a, range_b are read), so that every shard plans its LDS spline windows from the same frames as a single

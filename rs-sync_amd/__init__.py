@@ -15,3 +15,4 @@ from . import quality  # noqa: F401
 from . import track  # noqa: F401
 from . import features  # noqa: F401
 from . import readout  # noqa: F401
+from . import lens  # noqa: F401

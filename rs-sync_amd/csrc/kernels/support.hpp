@@ -186,6 +186,64 @@ __global__ __launch_bounds__(kBlock) void retime_pixels_kernel(RetimeParams p) {
     }
 }
 
+// Re-lens kernel: a new lens for the pixel frames without repacking them (the lens sweep, rssync_c.h: rssync_ext_lens_sweep).
+// A lens changes the ray directions as well as the row times, so per pair it reads the whole raw pixel record (32 B, two
+// double2) and rewrites ALL packed streams of the pair (96 B) with the arithmetic of pack_frames_kernel's pixel branch --
+// rs::pixel_to_ray and pixel_knot_offset, the same text -- against the base knot of the frame table the launcher has just
+// installed.  The lens of a frame comes from a device table (9 doubles per frame, uniform across a block).  One thread per
+// pair; rays with a non-finite packed value are counted as the packing kernel counts them, reduced within the wave first
+// (one atomic per wave that met any).  Frames set as rays leave at once.
+struct RelensParams {
+    const double* raw;
+    const rship_pack_frame* pack; // the records of the last rship_pack_frames (raw offset, times, rows)
+    const FrameRec* frames;       // the new frame table (base_knot)
+    const double* lens;           // [n_frames][9]: ro, fx, fy, cx, cy, k1 .. k4
+    f4* rays_a;
+    f4* rays_b;
+    double2* q0;
+    double2* q1;
+    double2* q2;
+    double2* q3;
+    double start, fs;
+    uint32_t* bad; // this launch's counter
+};
+
+__global__ __launch_bounds__(kBlock) void relens_pixels_kernel(RelensParams p) {
+    const rship_pack_frame& fr = p.pack[blockIdx.x];
+    if (!fr.is_pixels) return;
+    const uint32_t n = fr.n_rays;
+    const double* L = p.lens + 9 * (size_t)blockIdx.x;
+    const rs::Lens lens{L[0], L[1], L[2], L[3], L[4], L[5], L[6], L[7], L[8]};
+    const double base = (double)p.frames[blockIdx.x].base_knot;
+    const double* rec = p.raw + fr.raw_offset;
+    uint32_t n_bad = 0;
+    for (uint32_t row = blockIdx.y * kBlock + threadIdx.x; row < n; row += gridDim.y * kBlock) {
+        double ra[3], rb[3], tsa, tsb;
+        const double2* src = (const double2*)(rec + 4 * (size_t)row);
+        const double2 a = src[0], b = src[1];
+        rs::pixel_to_ray(lens, a.x, a.y, fr.time_a, fr.rows, ra, &tsa);
+        rs::pixel_to_ray(lens, b.x, b.y, fr.time_b, fr.rows, rb, &tsb);
+        const double ta = pixel_knot_offset(lens.ro, a.y, fr.time_a, fr.rows, p.start, p.fs, base);
+        const double tb = pixel_knot_offset(lens.ro, b.y, fr.time_b, fr.rows, p.start, p.fs, base);
+        f4 o0, o1;
+        o0.x = (float)ra[0]; o0.y = (float)rb[0]; o0.z = (float)ra[1]; o0.w = (float)rb[1];
+        o1.x = (float)ra[2]; o1.y = (float)rb[2]; o1.z = (float)ta; o1.w = (float)tb;
+        const bool ok = finite_f(o0.x) && finite_f(o0.y) && finite_f(o0.z) && finite_f(o0.w) && finite_f(o1.x) &&
+                        finite_f(o1.y) && finite_f(o1.z) && finite_f(o1.w);
+        n_bad += ok ? 0u : 1u;
+        const size_t o = (size_t)fr.ray_offset + row;
+        p.rays_a[o] = o0;
+        p.rays_b[o] = o1;
+        p.q0[o] = double2{ra[0], rb[0]};
+        p.q1[o] = double2{ra[1], rb[1]};
+        p.q2[o] = double2{ra[2], rb[2]};
+        p.q3[o] = double2{ta, tb};
+    }
+    // (every thread of the block gets here: the early return above is uniform across it)
+    n_bad = wave_sum_u32(n_bad);
+    if (n_bad && (threadIdx.x & 63) == 0) atomicAdd(p.bad, n_bad);
+}
+
 // debug: the wave-level exact selection on caller-provided residuals (one wave per problem,
 // 2048 slots, NaN-padded), exactly as the LMedS kernel drives it
 __global__ __launch_bounds__(64) void debug_select_kernel(const float* __restrict__ vals, uint32_t n, uint32_t kq,

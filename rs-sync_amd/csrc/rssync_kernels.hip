@@ -144,6 +144,13 @@ struct rship_ctx {
     // stream (the asynchronous copies read them: released by sync_stream)
     DevBuf pack_list, retime_ro;
     std::vector<std::vector<char>> retime_staged;
+    // rship_relens_pixels: the lens table of the last re-lens and the counters of non-finite rays, one per slot the
+    // launcher was given (a sweep: one per candidate); h_relens_bad: the counters as the last wait that fetched them
+    // found them (rship_presync_batch_collect, rship_relens_counts), relens_fetched: nothing was enqueued since
+    DevBuf relens_lens, relens_bad;
+    uint32_t relens_slots = 0;
+    std::vector<uint32_t> h_relens_bad;
+    bool relens_fetched = false;
     std::vector<uint32_t> h_ray_off; // per table frame: its first ray (rship_retime_pixels checks its table against it)
     double pack_start = 0, pack_fs = 0;
     DevBuf mo_evals, mo_order; // per slot: evaluations of the last motion launch; launch order (longest first)
@@ -333,7 +340,7 @@ int ensure_pinned(rship_ctx* c, size_t bytes) {
 // names of the RSHIP_K_* launch kinds: the roctx range around a kind's launches (RSSYNC_ROCTX=1, roctx_ranges.hpp)
 const char* const kKindNames[RSHIP_K_COUNT] = {"rssync:K2 lmeds sweep", "rssync:K1 loss (trials)", "rssync:K3 motion L-BFGS", "rssync:window sums",
                                                "rssync:K2 GuessMotion search", "rssync:pack frames", "rssync:gyro pipeline", "rssync:K1 loss+gradient",
-                                               "rssync:retime pixels"};
+                                               "rssync:retime pixels", "rssync:relens pixels"};
 struct ProfScope {
     rship_ctx* c;
     int kind;
@@ -1153,7 +1160,7 @@ void rship_destroy(rship_ctx* c) {
     if (c->rccl_buf.p) (void)hipFree(c->rccl_buf.p);
     for (auto e : c->pool) (void)hipEventDestroy(e);
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
-    DevBuf* bufs[] = {&c->pack_list, &c->retime_ro, &c->coef, &c->coef64, &c->raw, &c->rays_a, &c->rays_b, &c->rays64, &c->frames, &c->sel, &c->M, &c->k, &c->grp, &c->grp_off,
+    DevBuf* bufs[] = {&c->pack_list, &c->retime_ro, &c->relens_lens, &c->relens_bad, &c->coef, &c->coef64, &c->raw, &c->rays_a, &c->rays_b, &c->rays64, &c->frames, &c->sel, &c->M, &c->k, &c->grp, &c->grp_off,
                       &c->plan_idx, &c->plan_chunk_off, &c->plan_win_off, &c->chunk_out, &c->win_out, &c->loop_state, &c->kd, &c->kd64, &c->init_h,
                       &c->frame_cost, &c->best_h, &c->costs, &c->part, &c->flags, &c->stats, &c->redo_mask, &c->redo_delays, &c->redo_count, &c->init_delays64, &c->dump, &c->dump_ncont,
                       &c->big_scratch, &c->mo_scratch, &c->mo_evals, &c->mo_order,
@@ -1624,6 +1631,7 @@ int rship_pack_frames(rship_ctx* c, const rship_frame* table, const rship_pack_f
     c->h_frame_n.assign(n_frames, 0);
     c->h_ray_off.assign(n_frames, 0);
     c->problem_dims.clear(); // (the host gives them again after packing: rship_set_problem_frames)
+    c->relens_slots = 0;     // (counters of re-lens launches belong to the streams they wrote)
     memset(c->cls_off, 0, sizeof(c->cls_off));
     memset(c->cls_max_n, 0, sizeof(c->cls_max_n));
     c->cls_used = 0;
@@ -1733,6 +1741,86 @@ int rship_retime_pixels(rship_ctx* c, const rship_frame* table, const double* ro
         hipLaunchKernelGGL(retime_pixels_kernel, dim3(n_frames, (max_n + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, p);
     }
     RS_HIP(hipGetLastError());
+    return 0;
+}
+
+// A new lens for the pixel frames of the table (rssync_c.h: rssync_ext_lens_sweep, rssync_ext_set_lens) without repacking
+// them: rship_retime_pixels' sibling for a change that moves the rays as well.  The frame table for the new lenses -- it
+// depends on a lens through its readout only, and the host computes it exactly as for rship_pack_frames -- and the lenses
+// (9 doubles per frame) are staged, copied in stream order, and relens_pixels_kernel rewrites every packed stream of the
+// pixel frames.  Nothing is waited for and, once the buffers have grown, nothing is allocated; selection, size classes and
+// plan of the sums stay, so that a batch of sweeps can re-lens between two of its sweeps.  Rays with a non-finite packed
+// value are counted into counter `bad_slot` of `n_bad_slots`; a call with bad_slot 0 (re)opens the set of counters and
+// clears them.  They come back with rship_presync_batch_collect's wait, or with rship_relens_counts.
+int rship_relens_pixels(rship_ctx* c, const rship_frame* table, const double* lenses, uint32_t n_frames, uint32_t bad_slot,
+                        uint32_t n_bad_slots) {
+    DeviceGuard dev_guard(c);
+    if (n_frames != c->n_frames) return set_err(c, "relens: the table must have the frames of the last rship_pack_frames");
+    if (!n_bad_slots || bad_slot >= n_bad_slots || n_bad_slots > 8192) return set_err(c, "relens: bad counter slot");
+    if (bad_slot != 0 && n_bad_slots != c->relens_slots) return set_err(c, "relens: the counters were opened for another number of slots");
+    for (uint32_t i = 0; i < n_frames; ++i) {
+        if (table[i].n_rays != c->h_frame_n[i] || table[i].ray_offset != c->h_ray_off[i])
+            return set_err(c, "relens: the table must have the frames of the last rship_pack_frames");
+        for (int q = 0; q < 9; ++q)
+            if (!std::isfinite(lenses[9 * (size_t)i + q])) return set_err(c, "relens: non-finite lens");
+    }
+    if (ensure(c, c->relens_bad, (size_t)n_bad_slots * 4)) return 1;
+    if (bad_slot == 0) {
+        RS_HIP(hipMemsetAsync(c->relens_bad.p, 0, (size_t)n_bad_slots * 4, c->stream));
+        c->relens_slots = n_bad_slots;
+    }
+    c->relens_fetched = false;
+    if (!n_frames) return 0;
+    // host copies that outlive this call: the copies below read them whenever the stream gets there
+    const size_t b_table = (size_t)n_frames * sizeof(rship_frame), b_lens = (size_t)n_frames * 9 * 8;
+    c->retime_staged.emplace_back(b_table + b_lens);
+    char* stage = c->retime_staged.back().data();
+    std::memcpy(stage, table, b_table);
+    std::memcpy(stage + b_table, lenses, b_lens);
+    if (install_frame_table(c, (const rship_frame*)stage, n_frames, true)) return 1;
+    uint32_t max_n = 0;
+    for (uint32_t i = 0; i < n_frames; ++i) max_n = std::max(max_n, c->h_frame_n[i]);
+    if (!max_n) return 0;
+    if (!c->pack_list.p) return set_err(c, "relens: no packed frames");
+    if (ensure(c, c->relens_lens, b_lens)) return 1;
+    RS_HIP(hipMemcpyAsync(c->relens_lens.p, stage + b_table, b_lens, hipMemcpyHostToDevice, c->stream));
+    const size_t tr = (size_t)c->total_rays;
+    RelensParams p{};
+    p.raw = (const double*)c->raw.p;
+    p.pack = (const rship_pack_frame*)c->pack_list.p;
+    p.frames = (const FrameRec*)c->frames.p;
+    p.lens = (const double*)c->relens_lens.p;
+    p.rays_a = (f4*)c->rays_a.p;
+    p.rays_b = (f4*)c->rays_b.p;
+    p.q0 = (double2*)c->rays64.p;
+    p.q1 = p.q0 + tr;
+    p.q2 = p.q1 + tr;
+    p.q3 = p.q2 + tr;
+    p.start = c->pack_start;
+    p.fs = c->pack_fs;
+    p.bad = (uint32_t*)c->relens_bad.p + bad_slot;
+    {
+        ProfScope ps(c, RSHIP_K_RELENS);
+        hipLaunchKernelGGL(relens_pixels_kernel, dim3(n_frames, (max_n + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, p);
+    }
+    RS_HIP(hipGetLastError());
+    return 0;
+}
+
+// The counters of the re-lens launches since the last call with slot 0: out[0 .. n).  Waits for the stream unless the
+// last wait that fetched them (rship_presync_batch_collect) already covers every launch.
+int rship_relens_counts(rship_ctx* c, uint32_t n, uint32_t* out) {
+    DeviceGuard dev_guard(c);
+    if (n > c->relens_slots) return set_err(c, "relens: more counters asked for than were opened");
+    if (!c->relens_fetched) {
+        const size_t bytes = (size_t)c->relens_slots * 4;
+        if (ensure_pinned(c, bytes + 64)) return 1;
+        if (bytes) RS_HIP(hipMemcpyAsync(c->pinned, c->relens_bad.p, bytes, hipMemcpyDeviceToHost, c->stream));
+        if (sync_stream(c)) return 1;
+        c->h_relens_bad.assign((const uint32_t*)c->pinned, (const uint32_t*)c->pinned + c->relens_slots);
+        c->relens_fetched = true;
+    }
+    for (uint32_t i = 0; i < n; ++i) out[i] = c->h_relens_bad[i];
     return 0;
 }
 
@@ -2022,12 +2110,19 @@ int rship_presync_batch_collect(rship_ctx* c, uint32_t n_cand, double* win_costs
     // the slots hold [rows][chunks + 1] / [rows][wins]; one copy each, then the host drops the padding column
     const size_t cs = (size_t)n_cand * (c->plan_chunks + 1), ws = (size_t)n_cand * c->plan_wins;
     const size_t b_win = n * ws * 8, b_chunk = n * cs * 8, b_flags = (size_t)n * 4;
-    if (ensure_pinned(c, b_win + b_chunk + b_flags + 64)) return 1;
+    if (ensure_pinned(c, b_win + b_chunk + b_flags + 128 + (size_t)c->relens_slots * 4)) return 1;
     char* h = (char*)c->pinned;
     RS_HIP(hipMemcpyAsync(h, c->win_out.p, b_win, hipMemcpyDeviceToHost, c->stream));
     RS_HIP(hipMemcpyAsync(h + b_win, c->chunk_out.p, b_chunk, hipMemcpyDeviceToHost, c->stream));
     RS_HIP(hipMemcpyAsync(h + b_win + b_chunk, c->flags.p, b_flags, hipMemcpyDeviceToHost, c->stream));
+    // (a lens sweep: the counters of its re-lens launches ride along with this wait -- rship_relens_counts hands them out)
+    const size_t b_bad = c->relens_fetched ? 0 : (size_t)c->relens_slots * 4, o_bad = (b_win + b_chunk + b_flags + 63) / 64 * 64;
+    if (b_bad) RS_HIP(hipMemcpyAsync(h + o_bad, c->relens_bad.p, b_bad, hipMemcpyDeviceToHost, c->stream));
     if (sync_stream(c)) return 1;
+    if (b_bad) {
+        c->h_relens_bad.assign((const uint32_t*)(h + o_bad), (const uint32_t*)(h + o_bad) + c->relens_slots);
+        c->relens_fetched = true;
+    }
     if (win_costs) memcpy(win_costs, h, b_win);
     if (chunk_costs) {
         const double* src = (const double*)(h + b_win);

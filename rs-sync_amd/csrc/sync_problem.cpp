@@ -60,6 +60,10 @@ thread_local std::string g_last_error;
 // ABI (tests/cpu_device/rship_cpu.cpp), which does not define it.  Without it a new readout is installed by repacking the
 // frames (frames_dirty_), which gives the same bits; librssync_core.so always has it (it links with --no-undefined).
 extern "C" int rship_retime_pixels(rship_ctx* c, const rship_frame* table, const double* ro, uint32_t n_frames) __attribute__((weak));
+// ... and the re-lens launcher with its counters (a new lens: the rays change too), on the same terms
+extern "C" int rship_relens_pixels(rship_ctx* c, const rship_frame* table, const double* lenses, uint32_t n_frames, uint32_t bad_slot,
+                                   uint32_t n_bad_slots) __attribute__((weak));
+extern "C" int rship_relens_counts(rship_ctx* c, uint32_t n, uint32_t* out) __attribute__((weak));
 
 // Gyro conditioning likewise: the product has no CPU path for it, so a device layer without these two refuses the setting
 // (set_gyro_conditioning) instead of emulating it.
@@ -198,6 +202,22 @@ HostFrame with_readout(const HostFrame& f, double ro) {
     return g;
 }
 
+// ... and with a whole lens {ro, fx, fy, cx, cy, k1 .. k4} (ro >= 0): what the host notes of a frame -- its row times --
+// depends on the lens through ro alone; the other eight entries are only handed on to the device
+HostFrame with_lens(const HostFrame& f, const double lens[9]) {
+    HostFrame g = with_readout(f, lens[0]);
+    std::copy(lens + 1, lens + 9, g.lens + 1);
+    return g;
+}
+
+// what makes a lens unusable, or NULL (the lens sweep and set_lens complain before anything is touched)
+const char* lens_complaint(const double lens[9]) {
+    if (!all_finite(lens, 9)) return "has non-finite entries";
+    if (!(lens[1] > 0) || !(lens[2] > 0)) return "needs positive focal lengths fx, fy";
+    if (lens[0] < 0) return "needs a non-negative readout ro";
+    return nullptr;
+}
+
 class SyncProblemHip final : public ISyncProblem {
    public:
     SyncProblemHip();
@@ -225,6 +245,9 @@ class SyncProblemHip final : public ISyncProblem {
     void readout_sweep(const double* readouts, size_t n_ro, double initial_delay, int64_t frame_begin, int64_t frame_end,
                        double search_step, double search_radius, double* costs, double* delays);
     void set_readout(double ro);
+    void lens_sweep(const double* lenses, size_t n_lens, double initial_delay, int64_t frame_begin, int64_t frame_end,
+                    double search_step, double search_radius, double* costs, double* delays);
+    void set_lens(const double lens[9]);
     void set_gyro_conditioning(const rssync_gyro_conditioning* cfg);
     void gyro_conditioned(double* rates, size_t cap, size_t* n, double* sample_rate, double* first_timestamp);
     uint64_t seed = 0x5EED0000ULL;
@@ -419,8 +442,14 @@ class SyncProblemHip final : public ISyncProblem {
     void pack_frames();
     rship_frame frame_record(int64_t id, const HostFrame& f, double* base) const;
     // the devices catch up with the readouts frames_ holds: re-timed (rship_retime_pixels) or, without the launcher, repacked
-    void refresh_readouts();
+    void refresh_readouts() { refresh_pixel_frames(false, 0, 1); }
     bool can_retime() const { return rship_retime_pixels != nullptr; }
+    // the same for the LENSES frames_ holds (with_lens): re-lensed (rship_relens_pixels, non-finite rays counted into
+    // counter bad_slot of n_bad_slots) or repacked; relens_bad: the counters 0 .. n summed over the devices (waits)
+    void refresh_pixel_frames(bool lenses, uint32_t bad_slot, uint32_t n_bad_slots);
+    void refresh_lenses(uint32_t bad_slot = 0, uint32_t n_bad_slots = 1) { refresh_pixel_frames(true, bad_slot, n_bad_slots); }
+    bool can_relens() const { return rship_relens_pixels != nullptr && rship_relens_counts != nullptr; }
+    std::vector<uint32_t> relens_bad(uint32_t n);
     std::vector<rship_frame> table_; // the frame table the devices hold (ray offsets local to each shard)
     void accept_gyro(const rship_gyro_result& r);
     bool cond_on_ = false; // set_gyro_conditioning: the rates setters take the uniform route
@@ -1085,12 +1114,17 @@ void SyncProblemHip::pack_frames() {
 // re-timing launcher (the CPU test double), the frames are repacked at the next use.  Same bits either way: the table
 // records come from frame_record as pack_frames makes them, the kernel shares its row-time arithmetic with the packing
 // kernel (kernels/support.hpp: pixel_knot_offset).
-void SyncProblemHip::refresh_readouts() {
+//
+// `lenses`: the other eight lens entries may have changed too (with_lens), which moves the rays: the re-lens launcher
+// (rship_relens_pixels, kernels/support.hpp: relens_pixels_kernel -- the packing kernel's pixel branch) rewrites all packed
+// streams and counts the rays that came out non-finite, as the packing kernel does, into the counter the caller names
+// (relens_bad reads them).  A readout-only change still goes through the re-timing launcher.
+void SyncProblemHip::refresh_pixel_frames(bool lenses, uint32_t bad_slot, uint32_t n_bad_slots) {
     if (frames_dirty_ || table_.size() != frames_.size()) { frames_dirty_ = true; return; }
-    if (!can_retime()) { frames_dirty_ = true; return; }
+    if (lenses ? !can_relens() : !can_retime()) { frames_dirty_ = true; return; }
     const size_t nf = frames_.size();
     std::vector<rship_frame> table(table_);
-    std::vector<double> ro(nf, 0.0);
+    std::vector<double> ro(lenses ? 0 : nf, 0.0), lens(lenses ? 9 * nf : 0, 0.0);
     size_t i = 0;
     for (const auto& [id, f] : frames_) {
         if (f.from_pixels) {
@@ -1098,12 +1132,18 @@ void SyncProblemHip::refresh_readouts() {
             const uint32_t off = table[i].ray_offset;
             table[i] = frame_record(id, f, &base);
             table[i].ray_offset = off;
-            ro[i] = f.lens[0];
+            if (lenses) std::copy(f.lens, f.lens + 9, lens.begin() + 9 * i);
+            else ro[i] = f.lens[0];
         }
         ++i;
     }
-    for (Shard& sh : shards_)
-        hip_check(sh, rship_retime_pixels(sh.ctx, table.data() + sh.t0, ro.data() + sh.t0, sh.t1 - sh.t0), "retime pixels");
+    for (Shard& sh : shards_) {
+        if (lenses)
+            hip_check(sh, rship_relens_pixels(sh.ctx, table.data() + sh.t0, lens.data() + 9 * (size_t)sh.t0, sh.t1 - sh.t0, bad_slot, n_bad_slots),
+                      "relens pixels");
+        else
+            hip_check(sh, rship_retime_pixels(sh.ctx, table.data() + sh.t0, ro.data() + sh.t0, sh.t1 - sh.t0), "retime pixels");
+    }
     if (shards_.size() > 1)
         for (Shard& sh : shards_) hip_check(sh, rship_set_problem_frames(sh.ctx, table.data(), (uint32_t)nf), "problem frames");
     table_ = std::move(table);
@@ -1243,6 +1283,162 @@ void SyncProblemHip::readout_sweep(const double* readouts, size_t n_ro, double i
         delays[i] = cand[best];
     }
     if (redone) own();
+    restore.armed = false;
+}
+
+// counters 0 .. n of the re-lens launches since the last refresh_lenses(0, ...), summed over this object's devices
+std::vector<uint32_t> SyncProblemHip::relens_bad(uint32_t n) {
+    std::vector<uint32_t> total(n, 0u), part(n, 0u);
+    for (Shard& sh : shards_) {
+        hip_check(sh, rship_relens_counts(sh.ctx, n, part.data()), "relens counts");
+        for (uint32_t i = 0; i < n; ++i) total[i] += part[i];
+    }
+    return total;
+}
+
+// rssync_ext_set_lens: every pixel frame as if set again with this lens.  A lens that turns rays non-finite is met as
+// after setting the frames again: the frames are left to be repacked, and the next use complains (pack_frames).
+void SyncProblemHip::set_lens(const double lens[9]) {
+    rs::RoctxRange roctx_range("rssync:set_lens");
+    if (const char* why = lens_complaint(lens)) panic(std::string("set-lens: the lens ") + why);
+    for (auto& [id, f] : frames_)
+        if (f.from_pixels) f = with_lens(f, lens);
+    sel_.clear();
+    window_key_.clear();
+    refresh_lenses();
+    if (!frames_dirty_ && relens_bad(1)[0]) frames_dirty_ = true;
+}
+
+// rssync_ext_lens_sweep: the readout sweep's sibling for the whole lens.  For each candidate lens, every frame of
+// [frame_begin, frame_end) as if set again with it, then PreSync; the frames keep their own lenses afterwards.  The same
+// pipeline: selection, plan and candidate delays do not depend on the lens, so per candidate the frame table is installed,
+// the packed streams are re-lensed (rship_relens_pixels) and the sweep is enqueued into its result slot; after the last
+// candidate the frames' own lenses are restored on the stream, then ONE wait and, with ranks, ONE exchange.  The same
+// route rule (rs::plan_sweep_pipelined) and the same plain route -- no launcher, RSSYNC_SWEEP_PIPELINE=0, too many
+// candidates, a sliced delay list -- the same redo of a candidate that flags near-static pairs, the same arg-min rule.
+// What a lens adds: it can turn rays non-finite, which setting the frames again would complain about at the next use
+// (pack_frames).  The re-lens kernel counts such rays per candidate; the counts come back with the batch's wait, ride in the
+// exchange as the flag bits do, and the first candidate with any fails the call as the loop would have failed there.
+void SyncProblemHip::lens_sweep(const double* lenses, size_t n_lens, double initial_delay, int64_t frame_begin,
+                                int64_t frame_end, double search_step, double search_radius, double* costs, double* delays) {
+    rs::RoctxRange roctx_range("rssync:lens_sweep");
+    if (n_lens < 1) panic("lens sweep: no lenses");
+    for (size_t i = 0; i < n_lens; ++i)
+        if (const char* why = lens_complaint(lenses + 9 * i)) panic("lens sweep: lens " + std::to_string(i) + " " + why);
+    for (const auto& [id, f] : frames_)
+        if (id >= frame_begin && id < frame_end && !f.from_pixels)
+            panic("lens sweep: frame " + std::to_string(id) + " was set as rays (rssync_set_track_result): it has no pixels to undistort");
+    ensure_device();
+    // every way out -- a panic in throwing mode included -- leaves each frame with its own lens
+    struct Restore {
+        SyncProblemHip* s;
+        std::map<int64_t, HostFrame> saved;
+        bool armed = true;
+        ~Restore() {
+            if (!armed) return;
+            s->frames_ = std::move(saved);
+            s->frames_dirty_ = true; // (repacked at the next use: nothing is asked of a device that may have failed)
+        }
+    } restore{this, frames_};
+    auto bad_rays = [&](size_t i, uint64_t count) {
+        panic("lens sweep: lens " + std::to_string(i) + ": non-finite numbers in rays (" + std::to_string(count) + " tracks; lens parameters?)");
+    };
+    auto install = [&](const double* lens, uint32_t slot, uint32_t n_slots) { // the range's frames with this lens, the others with their own
+        for (auto& [id, f] : frames_)
+            if (id >= frame_begin && id < frame_end) f = with_lens(restore.saved.at(id), lens);
+        refresh_lenses(slot, n_slots);
+    };
+    auto own = [&](uint32_t slot, uint32_t n_slots) {
+        frames_ = restore.saved;
+        refresh_lenses(slot, n_slots);
+    };
+    auto one_by_one = [&](size_t i) {
+        install(lenses + 9 * i, 0, 1);
+        if (!frames_dirty_) // (re-lensed: the count is here; repacked: PreSync's packing complains)
+            if (const uint32_t b = relens_bad(1)[0]) bad_rays(i, b);
+        const std::pair<double, double> r = PreSync(initial_delay, frame_begin, frame_end, search_step, search_radius);
+        costs[i] = r.first;
+        delays[i] = r.second;
+    };
+    const char* env_pipeline = std::getenv("RSSYNC_SWEEP_PIPELINE");
+    const bool no_pipeline = env_pipeline && env_pipeline[0] == '0';
+    select(frame_begin, frame_end);
+    std::vector<double> cand; // the candidates are whatever this double loop yields (core_private.cpp:69-70), as in PreSync
+    for (double delay = initial_delay - search_radius; delay < initial_delay + search_radius; delay += search_step) {
+        cand.push_back(delay);
+        if (cand.size() > 50000000) panic("pre-sync: more than 5e7 candidate delays");
+    }
+    if (cand.empty()) panic("pre-sync: empty candidate list");
+    const size_t n = cand.size(), W = plan_windows_;
+    if (no_pipeline || !can_relens() || !rs::plan_sweep_pipelined(n_lens, n, W, sel_.size(), frame_begin, frame_end, distributed())) {
+        for (size_t i = 0; i < n_lens; ++i) one_by_one(i);
+        own(0, 1);
+        restore.armed = false;
+        return;
+    }
+    std::vector<int32_t> kd(n), kd64(n);
+    std::vector<float> fd(n);
+    std::vector<double> fd64(n);
+    for (size_t i = 0; i < n; ++i) {
+        const DelaySplit sp = split_delay(cand[i], fs_);
+        kd[i] = sp.kd; fd[i] = sp.fd;
+        const DelaySplit64 sp64 = split_delay64(cand[i], fs_);
+        kd64[i] = sp64.kd; fd64[i] = sp64.fd;
+    }
+    for (Shard& sh : shards_) hip_check(sh, rship_presync_batch_begin(sh.ctx, (uint32_t)n_lens, (uint32_t)n), "presync batch");
+    struct CloseBatch { // a panic between here and the collect must not leave the contexts in a batch
+        SyncProblemHip* s;
+        bool armed = true;
+        ~CloseBatch() {
+            if (armed)
+                for (Shard& sh : s->shards_)
+                    if (sh.ctx) (void)rship_presync_batch_begin(sh.ctx, 0, 0);
+        }
+    } close_batch{this};
+    const uint32_t n_slots = (uint32_t)n_lens + 1; // a counter per candidate, and one for the restoring launch
+    for (size_t i = 0; i < n_lens; ++i) {
+        install(lenses + 9 * i, (uint32_t)i, n_slots);
+        for (Shard& sh : shards_)
+            hip_check(sh, rship_presync_enqueue(sh.ctx, kd.data(), fd.data(), kd64.data(), fd64.data(), (uint32_t)n, 20 /* core_private.cpp:77 */,
+                                                0u, seed, 0, 0),
+                      "presync");
+    }
+    own((uint32_t)n_lens, n_slots); // (enqueued behind the last sweep: the collect's wait covers it)
+    // ONE wait per device: all lenses' sums, [lens][candidate] rows, and the counters
+    std::vector<double> all(n_lens * n * W + 1, 0.0);
+    std::vector<uint32_t> flags(n_lens, 0u), fl_sh(n_lens);
+    combine(n_lens * n, W, [&](Shard& sh, double* win, double* chunk) {
+        hip_check(sh, rship_presync_batch_collect(sh.ctx, (uint32_t)n, win, chunk, fl_sh.data()), "presync batch");
+        for (size_t i = 0; i < n_lens; ++i) flags[i] |= fl_sh[i];
+    }, all.data());
+    close_batch.armed = false;
+    const std::vector<uint32_t> bad = relens_bad((uint32_t)n_lens);
+    // one exchange for the whole matrix; the flag bits ride along as small integers (five per lens), and the counts
+    std::vector<double> buf(all.begin(), all.begin() + n_lens * n * W);
+    for (size_t i = 0; i < n_lens; ++i)
+        for (int b = 0; b < 5; ++b) buf.push_back((double)((flags[i] >> b) & 1u));
+    for (size_t i = 0; i < n_lens; ++i) buf.push_back((double)bad[i]);
+    if (distributed()) reduce(buf.data(), buf.size());
+    bool redone = false;
+    for (size_t i = 0; i < n_lens; ++i) {
+        const double n_bad = buf[n_lens * n * W + 5 * n_lens + i];
+        if (n_bad > 0) bad_rays(i, (uint64_t)n_bad); // (every rank alike: the counts were summed)
+        const double* fl = buf.data() + n_lens * n * W + 5 * i;
+        const uint32_t fa = (fl[0] > 0 ? 1u : 0u) | (fl[1] > 0 ? 2u : 0u) | (fl[2] > 0 ? 4u : 0u) | (fl[3] > 0 ? 8u : 0u);
+        if (const char* msg = presync_panic(fa)) panic(msg);
+        if (fl[4] > 0) { // near-static pairs on some rank: this lens once more, with their fp64 form (every rank agrees: the flag was summed)
+            one_by_one(i);
+            redone = true;
+            continue;
+        }
+        const double* c = buf.data() + i * n * W; // (W == 1: select() makes one window)
+        size_t best = 0; // *std::min_element over pair(cost, delay) (core_private.cpp:89)
+        for (size_t k = 1; k < n; ++k)
+            if (std::make_pair(c[k * W], cand[k]) < std::make_pair(c[best * W], cand[best])) best = k;
+        costs[i] = c[best * W];
+        delays[i] = cand[best];
+    }
+    if (redone) own(0, 1);
     restore.armed = false;
 }
 
@@ -2561,6 +2757,28 @@ int rssync_ext_readout_sweep(rssync_problem* p, const double* readouts, int n, d
 }
 
 int rssync_ext_set_readout(rssync_problem* p, double ro) { return guarded([&] { p->impl->set_readout(ro); }); }
+
+int rssync_ext_lens_sweep(rssync_problem* p, const rssync_lens* lenses, int n, double initial_delay, int64_t frame_begin,
+                          int64_t frame_end, double search_step, double search_radius, double* costs, double* delays) {
+    return guarded([&] {
+        if (n < 1 || !lenses) panic("lens sweep: no lenses");
+        std::vector<double> l(9 * (size_t)n);
+        for (int i = 0; i < n; ++i) {
+            const rssync_lens& s = lenses[i];
+            const double v[9] = {s.ro, s.fx, s.fy, s.cx, s.cy, s.k1, s.k2, s.k3, s.k4};
+            std::copy(v, v + 9, l.begin() + 9 * (size_t)i);
+        }
+        p->impl->lens_sweep(l.data(), (size_t)n, initial_delay, frame_begin, frame_end, search_step, search_radius, costs, delays);
+    });
+}
+
+int rssync_ext_set_lens(rssync_problem* p, const rssync_lens* lens) {
+    return guarded([&] {
+        if (!lens) panic("set-lens: no lens");
+        const double l[9] = {lens->ro, lens->fx, lens->fy, lens->cx, lens->cy, lens->k1, lens->k2, lens->k3, lens->k4};
+        p->impl->set_lens(l);
+    });
+}
 
 int rssync_ext_frame_rays(rssync_problem* p, int64_t frame, float* a4, float* b4, size_t cap, size_t* n) {
     return guarded([&] {

@@ -105,6 +105,9 @@ SIGNATURES = {
     "rssync_ext_readout_sweep": (C.c_int, [C.c_void_p, _PD, C.c_int, C.c_double, C.c_int64, C.c_int64, C.c_double,
                                            C.c_double, _PD, _PD]),
     "rssync_ext_set_readout": (C.c_int, [C.c_void_p, C.c_double]),
+    "rssync_ext_lens_sweep": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int64, C.c_int64, C.c_double,
+                                        C.c_double, _PD, _PD]),
+    "rssync_ext_set_lens": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rssync_ext_frame_rays": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t,
                                         C.POINTER(C.c_size_t)]),
     "rssync_ext_pre_sync_windows": (C.c_int, [C.c_void_p, C.c_double, _PI64, _PI64, C.c_int, C.c_double, C.c_double,
@@ -614,6 +617,27 @@ class SyncProblem:
         """Every pixel frame as if set again with lens.ro = ro (s)."""
         self._check(self._lib.rssync_ext_set_readout(self._h, float(ro)))
 
+    def lens_sweep(self, lenses, initial_delay, frame_begin, frame_end, search_step, search_radius):
+        """PreSync with every pixel frame of [frame_begin, frame_end) set again with each candidate lens (n x 9, the
+        order of set_track_pixels' lens: ro, fx, fy, cx, cy, k1 .. k4) -> (costs[n], delays[n]); the lowest cost marks
+        the lens that fits (rssync_amd.lens.estimate_lens searches with it).  The frames keep their own lens."""
+        L = np.ascontiguousarray(lenses, np.float64)
+        if L.ndim != 2 or L.shape[1] != 9:
+            raise ValueError("lenses must be (n, 9): ro, fx, fy, cx, cy, k1, k2, k3, k4 per row")
+        n = L.shape[0]
+        costs, delays = np.zeros(n), np.zeros(n)
+        self._check(self._lib.rssync_ext_lens_sweep(self._h, L.ctypes.data, n, float(initial_delay), int(frame_begin),
+                                                    int(frame_end), float(search_step), float(search_radius),
+                                                    _p(costs), _p(delays)))
+        return costs, delays
+
+    def set_lens(self, lens):
+        """Every pixel frame as if set again with this lens (ro, fx, fy, cx, cy, k1, k2, k3, k4)."""
+        L = np.ascontiguousarray(lens, np.float64)
+        if L.shape != (9,):
+            raise ValueError("lens = (ro, fx, fy, cx, cy, k1, k2, k3, k4)")
+        self._check(self._lib.rssync_ext_set_lens(self._h, L.ctypes.data))
+
     def frame_rays(self, frame, cap=2048):
         """The packed device streams of one frame: ({ax,bx,ay,by}, {az,bz,ta,tb}) as (n, 4) float32."""
         a4, b4, n = np.zeros((cap, 4), np.float32), np.zeros((cap, 4), np.float32), C.c_size_t()
@@ -872,7 +896,7 @@ class SyncProblem:
         self._check(self._lib.rssync_ext_profile_reset(self._h))
 
     def profile_get(self):
-        names = ["lmeds", "loss", "motion", "reduce", "init", "pixels", "gyro", "loss_grad", "retime"]
+        names = ["lmeds", "loss", "motion", "reduce", "init", "pixels", "gyro", "loss_grad", "retime", "relens"]
         out = {}
         for i, nm in enumerate(names):
             n, ms = C.c_uint64(), C.c_double()

@@ -17,17 +17,13 @@ lies on the edge of the grid or the three points do not open upwards), vertex_is
 readouts, costs, delays: the whole sweep."""
 
 
-def estimate_readout(problem, readouts, initial_delay, frame_begin, frame_end, search_step, search_radius):
-    """Sweep the candidate readouts (s, ascending) over the pixel frames of [frame_begin, frame_end) -> ReadoutEstimate.
-    The frames keep their own readout; install the estimate with problem.set_readout(est.readout)."""
-    ro = np.ascontiguousarray(readouts, np.float64).reshape(-1)
-    if ro.size > 1 and not np.all(np.diff(ro) > 0):
-        raise ValueError("readouts must be ascending")
-    costs, delays = problem.readout_sweep(ro, initial_delay, frame_begin, frame_end, search_step, search_radius)
-    k = min(range(ro.size), key=lambda i: (costs[i], delays[i]))
-    vertex, interior = float(ro[k]), False
-    if 0 < k < ro.size - 1:
-        x0, x1, x2 = ro[k - 1:k + 2]
+def grid_vertex(x, costs, k):
+    """The refinement rule of the grid searches (estimate_readout here, rssync_amd.lens.estimate_lens): the vertex of
+    the parabola through the arg-min k of an ascending grid x and its two neighbours, clamped to them -> (vertex,
+    interior).  Where k lies on the grid's edge or the three points do not open upwards: (x[k], False)."""
+    vertex, interior = float(x[k]), False
+    if 0 < k < len(x) - 1:
+        x0, x1, x2 = x[k - 1:k + 2]
         y0, y1, y2 = costs[k - 1:k + 2]
         # the parabola through the three points, in divided differences
         d01, d12 = (y1 - y0) / (x1 - x0), (y2 - y1) / (x2 - x1)
@@ -36,4 +32,16 @@ def estimate_readout(problem, readouts, initial_delay, frame_begin, frame_end, s
             vertex = float(0.5 * (x0 + x1) - d01 / (2.0 * curv))
             vertex = min(max(vertex, float(x0)), float(x2))
             interior = True
+    return vertex, interior
+
+
+def estimate_readout(problem, readouts, initial_delay, frame_begin, frame_end, search_step, search_radius):
+    """Sweep the candidate readouts (s, ascending) over the pixel frames of [frame_begin, frame_end) -> ReadoutEstimate.
+    The frames keep their own readout; install the estimate with problem.set_readout(est.readout)."""
+    ro = np.ascontiguousarray(readouts, np.float64).reshape(-1)
+    if ro.size > 1 and not np.all(np.diff(ro) > 0):
+        raise ValueError("readouts must be ascending")
+    costs, delays = problem.readout_sweep(ro, initial_delay, frame_begin, frame_end, search_step, search_radius)
+    k = min(range(ro.size), key=lambda i: (costs[i], delays[i]))
+    vertex, interior = grid_vertex(ro, costs, k)
     return ReadoutEstimate(float(ro[k]), float(delays[k]), float(costs[k]), vertex, interior, ro, costs, delays)
