@@ -83,16 +83,19 @@ def bisect(clear, steps):
 class limited_frame:
     """one frame's border as a function of the strength at a fixed zoom"""
 
-    def __init__(self, frame_time, zoom, target=None, sigma=SIGMA, **kw):
+    def __init__(self, frame_time, zoom, target=None, sigma=SIGMA, gyro=None, lens=None, size=None, delay=None, **kw):
+        """gyro, lens, size (rows, cols), delay: None = the scene's; kw: zr.frame_border's"""
         s = rr.scene()
-        self.scene, self.time, self.zoom, self.kw = s, frame_time, zoom, kw
-        self.own = sr.path64(s["gyro"], np.array([frame_time]), s["lens"][0], synth.D_TRUE, 0.0)[0]
-        self.goal = sr.path64(s["gyro"], np.array([frame_time]), s["lens"][0], synth.D_TRUE, sigma)[0] if target is None \
+        self.gyro, self.lens = s["gyro"] if gyro is None else gyro, s["lens"] if lens is None else lens
+        self.rows, self.cols = (rr.ROWS, rr.COLS) if size is None else size
+        self.delay = synth.D_TRUE if delay is None else delay
+        self.time, self.zoom, self.kw = frame_time, zoom, kw
+        self.own = sr.path64(self.gyro, np.array([frame_time]), self.lens[0], self.delay, 0.0)[0]
+        self.goal = sr.path64(self.gyro, np.array([frame_time]), self.lens[0], self.delay, sigma)[0] if target is None \
             else np.asarray(target, np.float64)
 
     def clear(self, a, mode=PLAIN, tol=0.0):
-        s = self.scene
-        fb = zr.frame_border(s["gyro"], s["lens"], rr.ROWS, rr.COLS, self.time, synth.D_TRUE, target=unit(blend(self.own, self.goal, a)),
+        fb = zr.frame_border(self.gyro, self.lens, self.rows, self.cols, self.time, self.delay, target=unit(blend(self.own, self.goal, a)),
                              **self.kw)
         return fb.clear(self.zoom, mode, tol)
 

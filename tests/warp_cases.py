@@ -153,13 +153,18 @@ def stab_camera_lens(L, rows, cols, zoom=STAB_ZOOM, out_size=None):
 
 
 @functools.lru_cache(maxsize=None)
-def stab_case(name, motion):
+def stab_case(name, motion, camera=sr.LENS, out_size=None):
+    """out_size: (cols, rows) of the output, None = the input's.  A PINHOLE camera gives every pixel a ray: all in range."""
     L, g = lens(name), gyro(motion)
     t, delay = frame_time(), synth.D_TRUE
-    kw = dict(sigma=STAB_SIGMA, zoom=STAB_ZOOM, camera=sr.LENS)
+    kw = dict(sigma=STAB_SIGMA, zoom=STAB_ZOOM, camera=camera, out_size=out_size)
     m64 = sr.map64(g, L, ROWS, COLS, t, delay, **kw)
     m32 = sr.map32(g, L, ROWS, COLS, t, delay, **kw)
-    inr, outr = range_masks(stab_camera_lens(L, ROWS, COLS), grid(ROWS, COLS))
+    if camera == sr.LENS:
+        ocols, orows = (COLS, ROWS) if out_size is None else out_size
+        inr, outr = range_masks(stab_camera_lens(L, ROWS, COLS, out_size=out_size), grid(orows, ocols))
+    else:
+        inr, outr = np.ones(m64.shape[:2], bool), np.zeros(m64.shape[:2], bool)
     compared = inr & near_frame(m64, ROWS, COLS)
     for a in (m64, inr, outr, compared):
         a.setflags(write=False)
@@ -169,6 +174,15 @@ def stab_case(name, motion):
 
 def stab_cases():
     return [(n, m) for n in STAB_LENSES for m in ("x1", "x20", "roll")]
+
+
+PINHOLE_LENSES = STAB_LENSES + ("aniso", "half")
+PINHOLE_OUT = (131, 73)                  # cols, rows of the other output size: the output camera's cx, cy are scaled
+
+
+def pinhole_cases():
+    """(lens, motion) of the stabiliser's PINHOLE camera, each at the input's size and at PINHOLE_OUT"""
+    return [(n, m) for n in PINHOLE_LENSES for m in ("x1", "x20", "roll")]
 
 
 # ---- points ------------------------------------------------------------------------------------------------------------

@@ -6,13 +6,17 @@
               arithmetic, with the frame's target and row table computed once instead of once per candidate zoom.  Three
               readings of "clear": plain; liberal (border pixels within a tolerance of a frame edge count as inside);
               conservative (they count as outside).  A device whose map is within that tolerance of the float64 one lies
-              between the last two.
+              between the last two.  With the LENS camera a border pixel beyond the zoomed camera's model range has no
+              ray and is outside under every reading; with a `margin` (relative, warp_cases.MARGIN) the pixels within it
+              of the range count with the near-edge pixels.  The default, 0, leaves the three readings as they were.
   smooth      the envelope
 
 The scene is rectify_reference.scene(): gyro knots 0 .. 2.4 s, the lens at 380 x 676, frames 32 .. 34.  TIMES are the nine
 frame times k / 30, k = 31 .. 39 (the scene's three frames are entries 1 .. 3), the delay is synth.D_TRUE, the path's
 sigma 0.2 s.
 """
+import functools
+
 import numpy as np
 
 import rectify_reference as rr
@@ -41,6 +45,15 @@ PLAIN, LIBERAL, CONSERVATIVE = 0, 1, 2
 CLEAR, NOT_CLEAR = 0, 1
 
 
+@functools.lru_cache(maxsize=None)
+def model_max(k):
+    """the largest theta (1 + k1 theta^2 + .. + k4 theta^8) on [0, pi / 2]: what |((u - cx) / fx, (v - cy) / fy)| of a pixel
+    the lens camera can image stays below (warp_cases.model_max, restated so that this module needs no case list)"""
+    th = np.linspace(0.0, np.pi / 2, 200001)
+    t2 = th * th
+    return float((th * (1 + t2 * (k[0] + t2 * (k[1] + t2 * (k[2] + t2 * k[3]))))).max())
+
+
 def bisect(clear, lo, hi, steps):
     """-> (zoom, status): include/rssync_zoom.h's procedure; 0.5 * (lo + hi) is one addition and one exact halving"""
     if not clear(hi):
@@ -61,8 +74,9 @@ class frame_border:
     zoom -- the target and the row table -- kept"""
 
     def __init__(self, gyro, lens, rows, cols, frame_time, delay, target=None, sigma=0.0, out_size=None, camera=sr.LENS, cam=None,
-                 iterations=3):
+                 iterations=3, margin=0.0):
         self.lens, self.rows, self.cols, self.camera, self.cam, self.iterations = lens, rows, cols, camera, cam, iterations
+        self.margin = margin
         self.out_cols, self.out_rows = (cols, rows) if out_size is None else out_size
         q_t = sr.path64(gyro, np.array([frame_time]), lens[0], delay, sigma)[0] if target is None else sr.unit(target)
         self.table = sr.row_table(gyro, lens, rows, frame_time, delay, q_t)
@@ -73,11 +87,24 @@ class frame_border:
         r = sr.rays(self.px, cam, self.lens, self.camera, np.float64)
         return sr.iterate(r, self.table, self.lens, self.rows, self.px[..., 1] * (self.rows / self.out_rows), self.iterations, np.float64)
 
+    def range_band(self, zoom):
+        """LENS camera -> (beyond, band) of the border pixels: beyond the zoomed camera's model range by more than the
+        relative `margin` (no ray: outside under every reading), and within the margin of it on either side (the device's
+        ray may or may not exist there: these count with the near-edge pixels).  PINHOLE: every pixel has a ray."""
+        if self.camera != sr.LENS:
+            return np.zeros(len(self.px), bool), np.zeros(len(self.px), bool)
+        fx, fy, cx, cy = sr.out_camera(self.lens, self.rows, self.cols, self.out_rows, self.out_cols, zoom, self.cam)
+        rd = np.hypot((self.px[..., 0] - cx) / fx, (self.px[..., 1] - cy) / fy)
+        mx = model_max(tuple(self.lens[5:]))
+        return rd > mx * (1 + self.margin), (rd >= mx * (1 - self.margin)) & (rd <= mx * (1 + self.margin))
+
     def clear(self, zoom, mode=PLAIN, tol=0.0):
         m = self.map(zoom)
-        outside = ~sr.inside(m, self.rows, self.cols)
+        outside = ~sr.inside(m, self.rows, self.cols)        # (a pixel without a ray has a NaN position: outside)
+        beyond, band = self.range_band(zoom) if self.margin > 0 else (False, False)
+        outside = outside | beyond
         if mode != PLAIN:
-            near = sr.near_edge(m, self.rows, self.cols, tol)
+            near = sr.near_edge(m, self.rows, self.cols, tol) | band
             outside = (outside & ~near) if mode == LIBERAL else (outside | near)
         return not outside.any()
 
