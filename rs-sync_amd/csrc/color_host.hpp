@@ -1,10 +1,12 @@
 // color_host.hpp -- what the colour front's public entry points do before the device runs: the formats' planes, the fills,
 // the chroma plane's lens, frame time and output camera (color_math.hpp), the planes' pitches, strides and extents.  Shared
-// by color_api.cpp and colorzoom_api.cpp (include/rssync_colorzoom.h resolves a call exactly as the colour front does).
+// by color_api.cpp, colorzoom_api.cpp (include/rssync_colorzoom.h resolves a call exactly as the colour front does) and
+// yuv_api.cpp (include/rssync_yuv.h: the 4:2:2 and 4:4:4 formats, which only its entry points take).
 #pragma once
 
 #include "../../include/rssync_color.h"
 #include "../../include/rssync_color16.h"
+#include "../../include/rssync_yuv.h"
 #include "color_hip.h"
 #include "color_math.hpp"
 #include "stabilize_host.hpp"
@@ -24,6 +26,12 @@ using namespace rssync_stab_host;
 
 inline bool is_16(int format) { return format >= RSSYNC_COLOR16_GRAY16 && format <= RSSYNC_COLOR16_I010; }
 
+// include/rssync_yuv.h's formats, and those of them in 16-bit containers
+inline bool is_yuv4(int format) {
+    return (format >= RSSYNC_YUV_I422 && format <= RSSYNC_YUV_I444) || (format >= RSSYNC_YUV_I210 && format <= RSSYNC_YUV_I410);
+}
+inline bool is_wide(int format) { return is_16(format) || (format >= RSSYNC_YUV_I210 && format <= RSSYNC_YUV_I410); }
+
 // the 8-bit format whose planes and geometry a 16-bit format has
 inline int sibling(int format) {
     switch (format) {
@@ -31,14 +39,23 @@ inline int sibling(int format) {
     case RSSYNC_COLOR16_P010:
     case RSSYNC_COLOR16_P016: return RSSYNC_COLOR_NV12;
     case RSSYNC_COLOR16_I010: return RSSYNC_COLOR_I420;
+    case RSSYNC_YUV_I210: return RSSYNC_YUV_I422;
+    case RSSYNC_YUV_P210:
+    case RSSYNC_YUV_P216: return RSSYNC_YUV_NV16;
+    case RSSYNC_YUV_I410: return RSSYNC_YUV_I444;
     default: return format;
     }
 }
 
 // bits of a sample value
-inline int depth(int format) { return !is_16(format) ? 8 : (format == RSSYNC_COLOR16_P010 || format == RSSYNC_COLOR16_I010) ? 10 : 16; }
+inline int depth(int format) {
+    if (!is_wide(format)) return 8;
+    return (format == RSSYNC_COLOR16_GRAY16 || format == RSSYNC_COLOR16_P016 || format == RSSYNC_YUV_P216) ? 16 : 10;
+}
 
 inline bool is_yuv(int format) { return sibling(format) == RSSYNC_COLOR_NV12 || sibling(format) == RSSYNC_COLOR_I420; }
+inline bool is_422(int format) { return sibling(format) == RSSYNC_YUV_I422 || sibling(format) == RSSYNC_YUV_NV16; }
+inline bool is_444(int format) { return sibling(format) == RSSYNC_YUV_I444; }
 
 struct Plane {
     size_t row_bytes, rows;
@@ -46,23 +63,32 @@ struct Plane {
 
 // the planes of a width x height frame -> their number; a 16-bit format's rows are twice its sibling's bytes
 inline int planes_of(int format, size_t w, size_t h, Plane* pl) {
-    const size_t b = is_16(format) ? 2 : 1;
+    const size_t b = is_wide(format) ? 2 : 1;
     switch (sibling(format)) {
     case RSSYNC_COLOR_GRAY8: pl[0] = {b * w, h}; return 1;
     case RSSYNC_COLOR_NV12: pl[0] = {b * w, h}; pl[1] = {b * w, h / 2}; return 2;
     case RSSYNC_COLOR_I420: pl[0] = {b * w, h}; pl[1] = pl[2] = {b * (w / 2), h / 2}; return 3;
+    case RSSYNC_YUV_I422: pl[0] = {b * w, h}; pl[1] = pl[2] = {b * (w / 2), h}; return 3;
+    case RSSYNC_YUV_NV16: pl[0] = pl[1] = {b * w, h}; return 2;
+    case RSSYNC_YUV_I444: pl[0] = pl[1] = pl[2] = {b * w, h}; return 3;
     default: pl[0] = {4 * w, h}; return 1;
     }
 }
 
 // format, sizes, parameters -> the configuration of both cameras.  wide: the call came through rssync_color16.h, whose
 // formats are the only ones it takes (and which the 8-bit entry points do not take); zoom_one: params->stab.zoom is not
-// read (the zooms come beside the call: colorzoom_api.cpp)
+// read (the zooms come beside the call: colorzoom_api.cpp); yuv4: the call came through rssync_yuv.h, whose formats are
+// the only ones it takes, whatever `wide` says
 inline rship_color_cfg resolve_color(rssync_problem* p, int format, size_t width, size_t height, const rssync_lens* lens, size_t out_width,
                               size_t out_height, double delay, const rssync_color_params* params, bool wide = false,
-                              bool zoom_one = false) {
-    if (wide && !is_16(format)) panic("color: format must be one of RSSYNC_COLOR16_*");
-    if (!wide && (format < RSSYNC_COLOR_GRAY8 || format > RSSYNC_COLOR_RGBA32)) panic("color: format must be one of RSSYNC_COLOR_*");
+                              bool zoom_one = false, bool yuv4 = false) {
+    if (yuv4) {
+        if (!is_yuv4(format)) panic("color: format must be one of RSSYNC_YUV_*");
+        wide = is_wide(format);
+    } else {
+        if (wide && !is_16(format)) panic("color: format must be one of RSSYNC_COLOR16_*");
+        if (!wide && (format < RSSYNC_COLOR_GRAY8 || format > RSSYNC_COLOR_RGBA32)) panic("color: format must be one of RSSYNC_COLOR_*");
+    }
     const int bits = depth(format), top = (1 << bits) - 1;
     rssync_color_params q = params ? *params : rssync_color_params{};
     if (q.chroma_site != RSSYNC_CHROMA_CENTER && q.chroma_site != RSSYNC_CHROMA_LEFT)
@@ -82,11 +108,16 @@ inline rship_color_cfg resolve_color(rssync_problem* p, int format, size_t width
                   std::to_string(out_width) + " x " + std::to_string(out_height) + ")");
         if (width < 4 || height < 4 || out_width < 4 || out_height < 4) panic("color: a 4:2:0 frame is too small (4 x 4 at least)");
     }
+    if (is_422(format)) {
+        if ((width | out_width) & 1)
+            panic("color: 4:2:2 frames need an even width (" + std::to_string(width) + " -> " + std::to_string(out_width) + ")");
+        if (width < 4 || out_width < 4) panic("color: a 4:2:2 frame is too small (4 pixels wide at least)");
+    }
     c.luma = resolve(p, width, height, lens, out_width, out_height, delay, &q.stab, zoom_one);
     if (!q.fill_set) {
         const int f = c.luma.fill;
         const int by_format[4][4] = {{f, 0, 0, 0}, {f, 128, 128, 0}, {f, 128, 128, 0}, {f, f, f, 255}};
-        for (int k = 0; k < 4; ++k) c.fill[k] = by_format[sibling(format)][k] << (bits - 8);
+        for (int k = 0; k < 4; ++k) c.fill[k] = by_format[is_422(format) || is_444(format) ? 1 : sibling(format)][k] << (bits - 8);
     }
     c.luma.fill = wide ? 0 : c.fill[0]; // (a 16-bit fill goes to the kernels from fill[] alone)
     c.chroma = c.luma;
@@ -100,6 +131,15 @@ inline rship_color_cfg resolve_color(rssync_problem* p, int format, size_t width
         rs::color_chroma_camera(&c.luma.lens[1], ox, oy, &c.chroma.lens[1]);
         rs::color_chroma_camera(c.luma.cam, ox, oy, c.chroma.cam);
         c.chroma_time = rs::color_chroma_time(0.0, c.luma.lens[0], oy, (double)height); // (0 + x is x: the launcher adds it to T)
+    }
+    if (is_422(format)) {
+        double ox;
+        rs::color_chroma422_offset(q.chroma_site, &ox);
+        c.chroma.width = c.luma.width / 2;
+        c.chroma.out_width = c.luma.out_width / 2;
+        rs::color_chroma422_camera(&c.luma.lens[1], ox, &c.chroma.lens[1]);
+        rs::color_chroma422_camera(c.luma.cam, ox, c.chroma.cam);
+        c.chroma_time = rs::color_chroma422_time(0.0);
     }
     return c;
 }
@@ -117,7 +157,7 @@ inline std::vector<Extent> check_image(const rssync_color_image* img, int format
     for (int k = 0; k < np; ++k) {
         const std::string name = std::string(what) + " plane " + std::to_string(k);
         if (!img->plane[k]) panic("color: " + name + " is NULL");
-        if (is_16(format) && (((uintptr_t)img->plane[k] | img->pitch[k]) & 1 || (n_frames > 1 && (img->stride[k] & 1))))
+        if (is_wide(format) && (((uintptr_t)img->plane[k] | img->pitch[k]) & 1 || (n_frames > 1 && (img->stride[k] & 1))))
             panic("color: alignment: pointer, pitch and frame stride of " + name + " must be multiples of 2");
         if (img->pitch[k] < pl[k].row_bytes)
             panic("color: pitch " + std::to_string(img->pitch[k]) + " of " + name + " < its row of " + std::to_string(pl[k].row_bytes) + " bytes");

@@ -7,6 +7,7 @@
 //   siting  chroma sample (cu, cv) sits at luma position (2 cu + ox, 2 cv + oy): CENTER (0.5, 0.5), LEFT (0, 0.5)
 //   lens    fx * 0.5, fy * 0.5, (cx - ox) * 0.5, (cy - oy) * 0.5; ro, k1 .. k4 unchanged        fp64 (color_chroma_camera)
 //   time    T_c = T + ro * (oy / height)                                                       fp64 (color_chroma_time)
+//   4:2:2   (2 cu + ox, cv): fx * 0.5, fy, (cx - ox) * 0.5, cy; T_c = T                        fp64 (color_chroma422_*)
 //   sample  rect_sample's taps and weights (color_taps) and its blend of four values (color_blend): bit for bit
 //   16 bit  the same blend on uint16 sample values (color_blend16), and P010's container: value = word >> 6, word = value << 6
 #pragma once
@@ -38,6 +39,20 @@ RS_LHD void color_chroma_camera(const double* cam, double ox, double oy, double*
 
 // the frame time of the chroma plane: its row 0 lies oy luma rows below the frame's
 RS_LHD double color_chroma_time(double frame_time, double ro, double oy, double height) { return frame_time + ro * (oy / height); }
+
+// 4:2:2 (include/rssync_yuv.h): chroma sample (cu, cv) sits at luma position (2 cu + ox, cv), the plane is halved in x alone
+RS_LHD void color_chroma422_offset(int site, double* ox) { *ox = site == 1 ? 0.0 : 0.5; }
+
+// a camera (fx, fy, cx, cy) of the luma grid as the camera of the 4:2:2 chroma grid: x halved, y kept
+RS_LHD void color_chroma422_camera(const double* cam, double ox, double* out) {
+    out[0] = cam[0] * 0.5;
+    out[1] = cam[1];
+    out[2] = (cam[2] - ox) * 0.5;
+    out[3] = cam[3];
+}
+
+// the frame time of a 4:2:2 chroma plane: its rows are the luma's
+RS_LHD double color_chroma422_time(double frame_time) { return frame_time; }
 
 // rect_sample's taps of an inside position: the upper left tap and the two weights
 struct ColorTaps {

@@ -29,6 +29,8 @@
 //   color_*_kernel     NV12, I420 and RGBA32 frames stabilised with all planes of a frame in one launch: both row tables,
 //                      the 4:2:0 warp per chroma sample with its 2 x 2 luma pixels, the RGBA warp (kernels/color.hpp).
 //   color16_*_kernel   the same for 16-bit containers: GRAY16, P010, P016 and I010 (kernels/color16.hpp).
+//   yuv4*_kernel       4:2:2 and 4:4:4 frames, 8-bit and in 16-bit containers: I422, NV16, I444, I210, P210, P216 and I410
+//                      (kernels/yuv.hpp).
 //   *bicubic*_kernel   the siblings of the kernels that write pixels with the 4 x 4 Catmull-Rom sampler (kernels/resample.hpp).
 //   zoom_*_kernel      the dynamic zoom: every frame's smallest clear zoom by an in-kernel bisection, and the stabiliser's
 //                      warp with one output camera per frame (kernels/zoom.hpp).
@@ -66,6 +68,7 @@
 #include "colorzoom_hip.h"
 #include "infill_hip.h"
 #include "colorinfill_hip.h"
+#include "yuv_hip.h"
 #include "device_math.hpp"
 #include "sync_math.hpp"
 #include "lens_math.hpp"
@@ -105,6 +108,7 @@ using rs::f4;
 #include "kernels/color.hpp"
 #include "kernels/color16.hpp"
 #include "kernels/resample.hpp"
+#include "kernels/yuv.hpp"
 #include "kernels/zoom.hpp"
 #include "kernels/limit.hpp"
 #include "kernels/colorzoom.hpp"
@@ -4565,11 +4569,27 @@ int rship_limit_fit(rship_ctx* c, const double* frame_times, uint32_t n_frames, 
 
 namespace {
 
-// the 16-bit formats (include/rssync_color16.h): GRAY16 16, P010 17, P016 18, I010 19
-bool color_is_16(int format) { return format >= 16 && format <= 19; }
+// the 16-bit formats (include/rssync_color16.h): GRAY16 16, P010 17, P016 18, I010 19; (include/rssync_yuv.h, beside
+// I422 32, NV16 33 and I444 34): I210 48, P210 49, P216 50, I410 51
+bool color_is_16(int format) { return (format >= 16 && format <= 19) || (format >= 48 && format <= 51); }
 
-// the 8-bit format whose planes and geometry a format has: GRAY16 -> GRAY8, P010 and P016 -> NV12, I010 -> I420
-int color_sibling(int format) { return format == 16 ? 0 : (format == 17 || format == 18) ? 1 : format == 19 ? 2 : format; }
+// the 8-bit format whose planes and geometry a format has: GRAY16 -> GRAY8, P010 and P016 -> NV12, I010 -> I420, I210 ->
+// I422, P210 and P216 -> NV16, I410 -> I444
+int color_sibling(int format) {
+    switch (format) {
+    case 16: return 0;
+    case 17: case 18: return 1;
+    case 19: return 2;
+    case 48: return 32;
+    case 49: case 50: return 33;
+    case 51: return 34;
+    }
+    return format;
+}
+
+// include/rssync_yuv.h's formats: a chroma plane halved in x alone, and none halved
+bool color_is_422(int format) { return color_sibling(format) == 32 || color_sibling(format) == 33; }
+bool color_is_444(int format) { return color_sibling(format) == 34; }
 
 // the planes of a width x height frame -> their number; a 16-bit format's rows are twice its sibling's bytes
 int color_planes(int format, uint32_t w, uint32_t h, rs::FramePlane* pl) {
@@ -4579,17 +4599,26 @@ int color_planes(int format, uint32_t w, uint32_t h, rs::FramePlane* pl) {
     case 1: pl[0] = {b * w, h}; pl[1] = {b * w, h / 2}; return 2;
     case 2: pl[0] = {b * w, h}; pl[1] = pl[2] = {b * (w / 2), h / 2}; return 3;
     case 3: pl[0] = {(size_t)w * 4, h}; return 1;
+    case 32: pl[0] = {b * w, h}; pl[1] = pl[2] = {b * (w / 2), h}; return 3;
+    case 33: pl[0] = pl[1] = {b * w, h}; return 2;
+    case 34: pl[0] = pl[1] = pl[2] = {b * w, h}; return 3;
     }
     return 0;
 }
 
 bool color_is_yuv(int format) { return color_sibling(format) == 1 || color_sibling(format) == 2; }
 
-// the largest sample value of a format: 8 bits, P010's and I010's ten, GRAY16's and P016's sixteen
-int32_t color_max(int format) { return !color_is_16(format) ? 255 : (format == 17 || format == 19) ? 1023 : 65535; }
+// the largest sample value of a format: 8 bits; P010's, I010's, I210's, P210's and I410's ten; GRAY16's, P016's and P216's
+// sixteen
+int32_t color_max(int format) {
+    return !color_is_16(format) ? 255 : (format == 17 || format == 19 || format == 48 || format == 49 || format == 51) ? 1023 : 65535;
+}
+
+// the formats whose words hold the value in their ten high bits: P010 and P210
+bool color_is_shifted(int format) { return format == 17 || format == 49; }
 
 int color_check(rship_ctx* c, const rship_color_cfg* g) {
-    if (!g || !((g->format >= 0 && g->format <= 3) || color_is_16(g->format))) return set_err(c, "color: bad configuration");
+    if (!g || !((g->format >= 0 && g->format <= 3) || (g->format >= 16 && g->format <= 19))) return set_err(c, "color: bad configuration");
     for (int k = 0; k < 4; ++k)
         if (g->fill[k] < 0 || g->fill[k] > color_max(g->format)) return set_err(c, "color: bad configuration");
     if (stab_check(c, &g->luma)) return 1;
@@ -4671,7 +4700,7 @@ ColorLaunch color_launch(rship_ctx* c, const rship_color_cfg* cfg, const rship_s
     K.G = stab_args(c, &L); // GRAY8: the stabiliser's kernel
     ColorArgs& A = K.A;
     A.luma = color_cam(&L, (const float4*)c->rect_rays.p);
-    if (color_is_yuv(cfg->format)) A.chroma = color_cam(&cfg->chroma, (const float4*)c->rect_rays_c.p);
+    if (color_is_yuv(cfg->format) || color_is_422(cfg->format)) A.chroma = color_cam(&cfg->chroma, (const float4*)c->rect_rays_c.p);
     A.width = L.width;
     A.height = L.height;
     A.out_width = L.out_width;
@@ -4679,7 +4708,7 @@ ColorLaunch color_launch(rship_ctx* c, const rship_color_cfg* cfg, const rship_s
     A.iterations = L.iterations;
     A.fill = (uint32_t)cfg->fill[0] | (uint32_t)cfg->fill[1] << 8 | (uint32_t)cfg->fill[2] << 16 | (uint32_t)cfg->fill[3] << 24;
     // the 16-bit kernels' fills as stored words: P010's values sit in the ten high bits
-    const uint32_t sh16 = cfg->format == 17 ? 6 : 0;
+    const uint32_t sh16 = color_is_shifted(cfg->format) ? 6 : 0;
     K.fill16_y = (uint32_t)cfg->fill[0] << sh16;
     K.fill16_uv = (uint32_t)cfg->fill[1] << sh16 | (uint32_t)cfg->fill[2] << (16 + sh16);
     if (color_is_16(cfg->format)) A.fill = 0;
@@ -4715,7 +4744,8 @@ int color_call(rship_ctx* c, const rship_color_image* in, uint32_t n_frames, con
                const rship_color_cfg* cfg, const rship_color_image* out, size_t budget_bytes, uint32_t radius, bool ray_maps,
                uint64_t* const* pairs, size_t n_pairs, PerChunk&& per_chunk) {
     const rship_stabilize_cfg L = color_luma(cfg);
-    const bool yuv = color_is_yuv(cfg->format);
+    // a 4:2:2 chroma plane has a camera and a ray map of its own, but the luma's rows: one table per frame
+    const bool yuv = color_is_yuv(cfg->format), c422 = color_is_422(cfg->format);
     const size_t n = n_frames, runs = 2 * n_pairs;
     rs::FrameLayout q;
     int np = 0;
@@ -4734,7 +4764,7 @@ int color_call(rship_ctx* c, const rship_color_image* in, uint32_t n_frames, con
     }
     RS_HIP(hipMemcpy(c->rect_times.p, times.data(), times.size() * 8, hipMemcpyHostToDevice));
     RS_HIP(hipMemsetAsync(c->rect_count.p, 0, runs * n * 8, c->stream));
-    if (stab_fill_targets(c, &L, targets, n) || (ray_maps && (stab_rays(c, &L) || (yuv && stab_rays(c, &cfg->chroma, true))))) return 1;
+    if (stab_fill_targets(c, &L, targets, n) || (ray_maps && (stab_rays(c, &L) || ((yuv || c422) && stab_rays(c, &cfg->chroma, true))))) return 1;
     Rows R = rows_args<Rows>(c, &L);
     R.rows_c = yuv ? L.height / 2 : 0;
     ColorLaunch K = color_launch(c, cfg, L);
@@ -4746,7 +4776,7 @@ int color_call(rship_ctx* c, const rship_color_image* in, uint32_t n_frames, con
             R.rows_tab = (float*)(C.base + P.off_tab[0]);
             R.rows_tab_c = (float*)(C.base + P.off_tab[1]);
             A.luma.rows_tab = R.rows_tab;
-            A.chroma.rows_tab = R.rows_tab_c;
+            A.chroma.rows_tab = c422 ? R.rows_tab : R.rows_tab_c;
             A.outside = (unsigned long long*)c->rect_count.p + C.f0;
             A.outside_c = A.outside + n;
             for (int k = 0; k < np; ++k) {
@@ -4883,6 +4913,90 @@ int rship_color_map(rship_ctx* c, int plane, double frame_time, const double* ta
     RS_HIP(hipMemcpy(c->rect_times.p, times, 16, hipMemcpyHostToDevice));
     if (stab_fill_targets(c, &cfg->luma, target, 1) || stab_rays(c, g, true)) return 1;
     return stab_map_run(c, g, c->rect_rays_c, 1, map_xy, on_dev);
+}
+
+} // extern "C"
+
+// ===========================================================================
+// 4:2:2 and 4:4:4 frames (kernels/yuv.hpp; declared in yuv_hip.h, called by yuv_api.cpp).  The colour front's pipeline
+// (color_call, color_frames_run) with these formats' planes: a 4:2:2 call has one row table per frame and a second cached
+// ray map, the chroma output camera's at out_width / 2 x out_height; a 4:4:4 call has one camera.
+
+namespace {
+
+int yuv_check(rship_ctx* c, const rship_color_cfg* g) {
+    if (!g || !(color_is_422(g->format) || color_is_444(g->format))) return set_err(c, "yuv: bad configuration");
+    for (int k = 0; k < 4; ++k)
+        if (g->fill[k] < 0 || g->fill[k] > color_max(g->format)) return set_err(c, "yuv: bad configuration");
+    if (stab_check(c, &g->luma)) return 1;
+    if (g->chroma_time != 0.0) return set_err(c, "yuv: bad configuration");
+    if (color_is_422(g->format)) {
+        const rship_stabilize_cfg &l = g->luma, &k = g->chroma;
+        if (stab_check(c, &k)) return 1;
+        if ((l.width | l.out_width) & 1u || l.width < 4 || l.out_width < 4 || k.width != l.width / 2 || k.height != l.height ||
+            k.out_width != l.out_width / 2 || k.out_height != l.out_height || k.camera != l.camera || k.iterations != l.iterations ||
+            k.filter != l.filter)
+            return set_err(c, "yuv: bad configuration");
+    }
+    return 0;
+}
+
+template <int C, int F> struct PickI422 { static constexpr auto kernel = yuv422_kernel<C, false, F>; };
+template <int C, int F> struct PickNv16 { static constexpr auto kernel = yuv422_kernel<C, true, F>; };
+template <int C, int F> struct PickI444 { static constexpr auto kernel = yuv444_kernel<C, F>; };
+template <int C, int F> struct PickI210 { static constexpr auto kernel = yuv422_16_kernel<C, false, 0, F>; };
+template <int C, int F> struct PickP210 { static constexpr auto kernel = yuv422_16_kernel<C, true, 6, F>; };
+template <int C, int F> struct PickP216 { static constexpr auto kernel = yuv422_16_kernel<C, true, 0, F>; };
+template <int C, int F> struct PickI410 { static constexpr auto kernel = yuv444_16_kernel<C, F>; };
+
+// cnt frames of ow x oh pixels through the format's kernel: a 4:2:2 format runs on the chroma plane's grid
+void yuv_launch(rship_ctx* c, int format, int camera, int filter, uint32_t ow, uint32_t oh, uint32_t cnt, const ColorLaunch& K) {
+    const uint32_t gw = color_is_422(format) ? ow / 2 : ow;
+    const dim3 grid((gw + kRectTW - 1) / kRectTW, (oh + kRectTH - 1) / kRectTH, cnt);
+    switch (format) {
+    case 32: camfilt_launch<PickI422>(c, camera, filter, grid, K.A); break;
+    case 33: camfilt_launch<PickNv16>(c, camera, filter, grid, K.A); break;
+    case 34: camfilt_launch<PickI444>(c, camera, filter, grid, K.A); break;
+    case 48: camfilt_launch<PickI210>(c, camera, filter, grid, K.A, K.fill16_y, K.fill16_uv); break;
+    case 49: camfilt_launch<PickP210>(c, camera, filter, grid, K.A, K.fill16_y, K.fill16_uv); break;
+    case 50: camfilt_launch<PickP216>(c, camera, filter, grid, K.A, K.fill16_y, K.fill16_uv); break;
+    case 51: camfilt_launch<PickI410>(c, camera, filter, grid, K.A, K.fill16_y, K.fill16_uv); break;
+    }
+}
+
+} // namespace
+
+extern "C" {
+
+int rship_yuv_frames(rship_ctx* c, const rship_color_image* in, uint32_t n_frames, const double* frame_times, const double* targets,
+                     const rship_color_cfg* cfg, const rship_color_image* out, uint64_t* n_outside, size_t budget_bytes) {
+    DeviceGuard dev_guard(c);
+    if (yuv_check(c, cfg)) return 1;
+    const rship_stabilize_cfg L = color_luma(cfg);
+    return color_frames_run(c, in, n_frames, frame_times, targets, cfg, out, n_outside, budget_bytes, true,
+                            [&](const ColorLaunch& K, uint32_t, uint32_t cnt) {
+        yuv_launch(c, cfg->format, L.camera, L.filter, L.out_width, L.out_height, cnt, K);
+    });
+}
+
+int rship_yuv_map(rship_ctx* c, int plane, double frame_time, const double* target, const rship_color_cfg* cfg, float* map_xy) {
+    {
+        DeviceGuard dev_guard(c);
+        if (yuv_check(c, cfg)) return 1;
+        if (plane != 0 && plane != 1) return set_err(c, "yuv: the format has no such plane");
+    }
+    // 4:4:4: every plane has the luma's camera
+    if (plane == 0 || color_is_444(cfg->format)) return rship_stabilize_map(c, frame_time, target, &cfg->luma, map_xy);
+    // the 4:2:2 chroma plane: the stabiliser's map of the chroma camera at the frame's time, against the frame's target
+    DeviceGuard dev_guard(c);
+    if (!map_xy) return set_err(c, "yuv: null pointer");
+    bool on_dev = false;
+    if (rect_pointer(c, map_xy, "the map", &on_dev, "yuv")) return 1;
+    const rship_stabilize_cfg* g = &cfg->chroma;
+    if (ensure(c, c->rect_times, 8)) return 1;
+    RS_HIP(hipMemcpy(c->rect_times.p, &frame_time, 8, hipMemcpyHostToDevice));
+    if (stab_fill_targets(c, &cfg->luma, target, 1) || stab_rays(c, g, true)) return 1;
+    return stab_map_run(c, g, c->rect_rays_c, 0, map_xy, on_dev);
 }
 
 } // extern "C"

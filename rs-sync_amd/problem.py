@@ -839,6 +839,26 @@ class SyncProblem:
         from . import color
         return color.color_map(self, fmt, plane, width, height, lens, frame_time, delay, **params)
 
+    def stabilize_yuv(self, fmt, frames, frame_times, lens, delay, **params):
+        """4:2:2 and 4:4:4 frames (rssync_amd.yuv: I422, NV16, I444, and with uint16 samples I210, P210, P216, I410) rendered
+        at the smoothed path's orientations, or at `targets`, all planes of a frame in one pass (include/rssync_yuv.h)
+        -> (planes in the layout of `frames`, a tuple of arrays or device tensors, n_outside (n, 2)).  params: targets,
+        out_size, out, chroma_site, fills, sigma, zoom, camera, out_camera, iterations, fill, filter."""
+        from . import yuv
+        return yuv.stabilize_yuv(self, fmt, frames, frame_times, lens, delay, **params)
+
+    def stabilize_yuv_budget(self, fmt, frames, frame_times, lens, delay, budget_bytes, **params):
+        """stabilize_yuv through the internal launcher with a device budget for its chunk slots (tests)."""
+        from . import yuv
+        return yuv.stabilize_yuv_budget(self, fmt, frames, frame_times, lens, delay, budget_bytes, **params)
+
+    def yuv_map(self, fmt, plane, width, height, lens, frame_time, delay, **params):
+        """-> float32 (rows, cols, 2): where stabilize_yuv looks every output sample of `plane` up (plane 1 of a 4:2:2
+        format: the chroma plane, out_width / 2 wide, in its own coordinates; of a 4:4:4 format: plane 0).  params: target,
+        out_size, chroma_site, sigma, zoom, camera, out_camera, iterations."""
+        from . import yuv
+        return yuv.yuv_map(self, fmt, plane, width, height, lens, frame_time, delay, **params)
+
     def stabilize_color_zoomed(self, fmt, frames, frame_times, lens, delay, zooms, **params):
         """stabilize_color with one zoom per frame (include/rssync_colorzoom.h, rssync_amd.colorzoom) -> (frames in the layout
         of `frames`, n_outside (n, 2)).  params: targets, out_size, out, chroma_site, fills, sigma, camera, out_camera,
