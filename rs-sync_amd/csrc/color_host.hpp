@@ -1,7 +1,8 @@
 // color_host.hpp -- what the colour front's public entry points do before the device runs: the formats' planes, the fills,
 // the chroma plane's lens, frame time and output camera (color_math.hpp), the planes' pitches, strides and extents.  Shared
 // by color_api.cpp, colorzoom_api.cpp (include/rssync_colorzoom.h resolves a call exactly as the colour front does) and
-// yuv_api.cpp (include/rssync_yuv.h: the 4:2:2 and 4:4:4 formats, which only its entry points take).
+// yuv_api.cpp and zoomyuv_api.cpp (include/rssync_yuv.h and include/rssync_zoomyuv.h: the 4:2:2 and 4:4:4 formats, which only
+// their entry points take).
 #pragma once
 
 #include "../../include/rssync_color.h"

@@ -69,6 +69,7 @@
 #include "infill_hip.h"
 #include "colorinfill_hip.h"
 #include "yuv_hip.h"
+#include "zoomyuv_hip.h"
 #include "device_math.hpp"
 #include "sync_math.hpp"
 #include "lens_math.hpp"
@@ -112,6 +113,7 @@ using rs::f4;
 #include "kernels/zoom.hpp"
 #include "kernels/limit.hpp"
 #include "kernels/colorzoom.hpp"
+#include "kernels/zoomyuv.hpp"
 #include "kernels/infill.hpp"
 #include "kernels/colorinfill.hpp"
 
@@ -4290,9 +4292,11 @@ int stab_map_run(rship_ctx* c, const rship_stabilize_cfg* g, const DevBuf& rays,
 }
 
 // c->stab_zooms <- the cameras of all frames, fp64 products as the configuration holds them for a constant zoom: per frame
-// (fx zoom, fy zoom) and, with per == 4, the chroma camera's, the same times 0.5 (color_chroma_camera).  `bad`: the
-// caller's message for a zoom that is not finite and > 0
-int zoom_cams(rship_ctx* c, const rship_stabilize_cfg* g, const double* zooms, uint32_t n_frames, size_t per, const char* bad) {
+// (fx zoom, fy zoom) and, with per == 4, the chroma camera's, the same times 0.5 (color_chroma_camera); chroma_y 1.0: fy
+// zoom kept as it is, the 4:2:2 rule (color_chroma422_camera).  `bad`: the caller's message for a zoom that is not finite
+// and > 0
+int zoom_cams(rship_ctx* c, const rship_stabilize_cfg* g, const double* zooms, uint32_t n_frames, size_t per, const char* bad,
+              double chroma_y = 0.5) {
     std::vector<double> cams((size_t)n_frames * per);
     for (uint32_t f = 0; f < n_frames; ++f) {
         if (!(zooms[f] > 0.0) || !std::isfinite(zooms[f])) return set_err(c, bad);
@@ -4301,7 +4305,7 @@ int zoom_cams(rship_ctx* c, const rship_stabilize_cfg* g, const double* zooms, u
         k[1] = g->cam[1] * zooms[f];
         if (per == 4) {
             k[2] = k[0] * 0.5;
-            k[3] = k[1] * 0.5;
+            k[3] = k[1] * chroma_y;
         }
     }
     if (n_frames) {
@@ -5051,6 +5055,69 @@ int rship_colorzoom_frames(rship_ctx* c, const rship_color_image* in, uint32_t n
         P.fill_y = K.fill16_y;
         P.fill_uv = K.fill16_uv;
         format_launch<PercamFamily>(c, cfg->format, L.camera, L.filter, L.out_width, L.out_height, cnt, P);
+    });
+}
+
+} // extern "C"
+
+// ===========================================================================
+// 4:2:2 and 4:4:4 frames with one zoom per frame (kernels/zoomyuv.hpp; declared in zoomyuv_hip.h, called by
+// zoomyuv_api.cpp).  rship_colorzoom_frames with the planes, the checks and the grid of rship_yuv_frames.
+
+namespace {
+
+template <int C, int F> struct PickFramecamI422 { static constexpr auto kernel = framecam_422_kernel<C, false, F>; };
+template <int C, int F> struct PickFramecamNv16 { static constexpr auto kernel = framecam_422_kernel<C, true, F>; };
+template <int C, int F> struct PickFramecamI444 { static constexpr auto kernel = framecam_444_kernel<C, F>; };
+template <int C, int F> struct PickFramecamI210 { static constexpr auto kernel = framecam_422_16_kernel<C, false, 0, F>; };
+template <int C, int F> struct PickFramecamP210 { static constexpr auto kernel = framecam_422_16_kernel<C, true, 6, F>; };
+template <int C, int F> struct PickFramecamP216 { static constexpr auto kernel = framecam_422_16_kernel<C, true, 0, F>; };
+template <int C, int F> struct PickFramecamI410 { static constexpr auto kernel = framecam_444_16_kernel<C, F>; };
+
+// yuv_launch with a camera per frame
+void framecam_launch(rship_ctx* c, int format, int camera, int filter, uint32_t ow, uint32_t oh, uint32_t cnt, const FramecamArgs& P) {
+    const uint32_t gw = color_is_422(format) ? ow / 2 : ow;
+    const dim3 grid((gw + kRectTW - 1) / kRectTW, (oh + kRectTH - 1) / kRectTH, cnt);
+    switch (format) {
+    case 32: camfilt_launch<PickFramecamI422>(c, camera, filter, grid, P); break;
+    case 33: camfilt_launch<PickFramecamNv16>(c, camera, filter, grid, P); break;
+    case 34: camfilt_launch<PickFramecamI444>(c, camera, filter, grid, P); break;
+    case 48: camfilt_launch<PickFramecamI210>(c, camera, filter, grid, P); break;
+    case 49: camfilt_launch<PickFramecamP210>(c, camera, filter, grid, P); break;
+    case 50: camfilt_launch<PickFramecamP216>(c, camera, filter, grid, P); break;
+    case 51: camfilt_launch<PickFramecamI410>(c, camera, filter, grid, P); break;
+    }
+}
+
+} // namespace
+
+extern "C" {
+
+int rship_zoomyuv_frames(rship_ctx* c, const rship_color_image* in, uint32_t n_frames, const double* frame_times, const double* targets,
+                         const rship_color_cfg* cfg, const double* zooms, const rship_color_image* out, uint64_t* n_outside,
+                         size_t budget_bytes) {
+    DeviceGuard dev_guard(c);
+    if (yuv_check(c, cfg)) return 1;
+    if (!zooms) return set_err(c, "zoomyuv: null pointer");
+    const rship_stabilize_cfg L = color_luma(cfg);
+    // the cameras of all frames: the luma's and the 4:2:2 chroma plane's, halved in x alone (4:4:4: the second pair is not read)
+    if (zoom_cams(c, &L, zooms, n_frames, 4, "zoomyuv: every zoom must be finite and > 0", 1.0)) return 1;
+    FramecamArgs P{};
+    P.cx = L.cam[2];
+    P.cy = L.cam[3];
+    P.cx_c = cfg->chroma.cam[2];
+    P.cy_c = cfg->chroma.cam[3];
+    P.k1 = L.lens[5];
+    P.k2 = L.lens[6];
+    P.k3 = L.lens[7];
+    P.k4 = L.lens[8];
+    return color_frames_run(c, in, n_frames, frame_times, targets, cfg, out, n_outside, budget_bytes, false,
+                            [&](const ColorLaunch& K, uint32_t f0, uint32_t cnt) {
+        P.C = K.A;
+        P.cams = (const double*)c->stab_zooms.p + 4 * (size_t)f0;
+        P.fill_y = K.fill16_y;
+        P.fill_uv = K.fill16_uv;
+        framecam_launch(c, cfg->format, L.camera, L.filter, L.out_width, L.out_height, cnt, P);
     });
 }
 

@@ -882,6 +882,29 @@ class SyncProblem:
         from . import colorzoom
         return colorzoom.dynamic_zoom_color(self, fmt, width, height, lens, frame_times, delay, lo, hi, window, **params)
 
+    def stabilize_yuv_zoomed(self, fmt, frames, frame_times, lens, delay, zooms, **params):
+        """stabilize_yuv with one zoom per frame (include/rssync_zoomyuv.h, rssync_amd.zoomyuv) -> (planes in the layout of
+        `frames`, n_outside (n, 2)).  params: targets, out_size, out, chroma_site, fills, sigma, camera, out_camera,
+        iterations, fill, filter."""
+        from . import zoomyuv
+        return zoomyuv.stabilize_yuv_zoomed(self, fmt, frames, frame_times, lens, delay, zooms, **params)
+
+    def stabilize_yuv_zoomed_budget(self, fmt, frames, frame_times, lens, delay, zooms, budget_bytes, **params):
+        """stabilize_yuv_zoomed through the internal launcher with a device budget for its chunk slots (tests)."""
+        from . import zoomyuv
+        return zoomyuv.stabilize_yuv_zoomed_budget(self, fmt, frames, frame_times, lens, delay, zooms, budget_bytes, **params)
+
+    def fit_zoom_yuv(self, fmt, width, height, lens, frame_times, delay, lo, hi, **params):
+        """-> (zooms (n,), status (n,)): every frame's smallest zoom in [lo, hi] that clears every plane of the format, a
+        4:2:2 chroma plane included.  params: steps, targets, out_size, chroma_site, sigma, camera, out_camera, iterations."""
+        from . import zoomyuv
+        return zoomyuv.fit_zoom_yuv(self, fmt, width, height, lens, frame_times, delay, lo, hi, **params)
+
+    def dynamic_zoom_yuv(self, fmt, width, height, lens, frame_times, delay, lo, hi, window, **params):
+        """-> (n,): fit_zoom_yuv followed by smooth_zooms; raises where a frame is not clear at `hi`."""
+        from . import zoomyuv
+        return zoomyuv.dynamic_zoom_yuv(self, fmt, width, height, lens, frame_times, delay, lo, hi, window, **params)
+
     def fit_strength(self, width, height, lens, frame_times, delay, **params):
         """-> (strengths (n,), status (n,)): how far every frame may follow its goal at a fixed zoom without showing a
         border, found by a bisection on the device (include/rssync_limit.h, rssync_amd.limit).  params: zoom, zooms, steps,
