@@ -3838,7 +3838,10 @@ rs::Lens rect_lens(const rship_rectify_cfg* g) {
 }
 
 // the ray of every output pixel: computed when the (lens, width, height) of the cached map is another.  The cache has two
-// places: the rectifier's and the stabiliser's map (and a colour call's luma map), and a 4:2:0 call's chroma map.
+// places: the rectifier's and the stabiliser's map (and a colour call's luma map), and the chroma map of a 4:2:0 or a 4:2:2
+// call, whichever came last (the key is the chroma plane's own camera and size, so a 4:2:2 map -- fy, cy and the height
+// unhalved -- never passes for the 4:2:0 map of the same frame; a 4:4:4 call and a call with a zoom per frame use no chroma
+// place and leave it as it is).
 int rect_rays_into(rship_ctx* c, const rship_rectify_cfg* g, DevBuf& rays, double* cached_key, bool& ok) {
     double key[10];
     for (int i = 0; i < 8; ++i) key[i] = g->lens[i + 1]; // (the readout time does not enter a ray)

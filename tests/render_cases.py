@@ -10,6 +10,7 @@ motions of tests/warp_cases.py.  Helpers only: numpy, warp_cases and the restate
            masks of the plane's own output camera, `compared` and the tolerance by wc.tolerance's rule
   fits     FIT_CASES / STRENGTH_CASES: zoom and strength fits whose three float64 readings agree in every frame
   infill   INFILL_CASES and the composition of a frame from per-candidate maps (compose_plane)
+  checks   check_map, padded and u32, which tests/test_gpu_yuv_lenses.py shares with tests/test_gpu_render_lenses.py
 """
 import functools
 
@@ -127,6 +128,33 @@ def outside_counts(name, motion, plane=0, site=cr.CENTER, camera=sr.LENS, zoom=Z
         c = plane_case(name, motion, plane, site, camera, zoom, None, k)
         out.append(int((~sr.inside(c["m64"], c["rows"], c["cols"])).sum()))
     return out
+
+
+# ---- checks shared by the device tests ----------------------------------------------------------------------------------
+def u32(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def check_map(what, got, c, rows, cols):
+    """test_gpu_warp_lenses' three assertions for one map of the device against a plane_case: compared samples within the
+    case's tolerance, the other in-range samples outside on both sides, out-of-range samples NaN -> the device's distance"""
+    assert got.shape == c["m64"].shape and got.dtype == np.float32, what
+    cmp_, inr, outr = c["compared"], c["in_range"], c["out_of_range"]
+    assert np.isfinite(got[inr]).all(), what
+    worst = float(np.abs(got.astype(np.float64) - c["m64"])[cmp_].max())
+    print("%s: %.3g px (tolerance %.3g, %d compared of %d in range, %d out of range)" % (what, worst, c["tol"], cmp_.sum(), inr.sum(), outr.sum()))
+    assert worst <= c["tol"], what
+    far = inr & ~cmp_
+    assert not sr.inside(got, rows, cols)[far].any() and not sr.inside(c["m64"], rows, cols)[far].any(), what
+    assert np.isnan(got[outr]).all(), what
+    return worst
+
+
+def padded(shape, dtype, value):
+    """an array with a frame of padding around (n, rows, cols[, c]) and the view into it"""
+    n, rows, cols = shape[:3]
+    whole = np.full((n, rows + 3, cols + 9) + tuple(shape[3:]), value, dtype)
+    return whole, whole[:, 1:1 + rows, 4:4 + cols]
 
 
 # ---- planes of noise ----------------------------------------------------------------------------------------------------

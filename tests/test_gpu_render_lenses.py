@@ -57,23 +57,8 @@ def problems(built):
     return {m: _problem(wc.gyro(m)) for m in rc.MOTIONS}
 
 
-def _u32(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _check_map(what, got, c, rows, cols):
-    """test_gpu_warp_lenses' three assertions for one map: compared samples within the case's tolerance, the other in-range
-    samples outside on both sides, out-of-range samples NaN -> the device's distance"""
-    assert got.shape == c["m64"].shape and got.dtype == np.float32, what
-    cmp_, inr, outr = c["compared"], c["in_range"], c["out_of_range"]
-    assert np.isfinite(got[inr]).all(), what
-    worst = float(np.abs(got.astype(np.float64) - c["m64"])[cmp_].max())
-    print("%s: %.3g px (tolerance %.3g, %d compared of %d in range, %d out of range)" % (what, worst, c["tol"], cmp_.sum(), inr.sum(), outr.sum()))
-    assert worst <= c["tol"], what
-    far = inr & ~cmp_
-    assert not sr.inside(got, rows, cols)[far].any() and not sr.inside(c["m64"], rows, cols)[far].any(), what
-    assert np.isnan(got[outr]).all(), what
-    return worst
+# the three assertions of a map, the padded output and the bit view: shared with tests/test_gpu_yuv_lenses.py
+_u32, _check_map, _padded = rc.u32, rc.check_map, rc.padded
 
 
 def _depth(fmt):
@@ -161,13 +146,6 @@ def test_b_plane_maps_of_the_colour_front_against_the_float64_reference(problems
 
 
 # c -----------------------------------------------------------------------------------------------------------------------
-def _padded(shape, dtype, value):
-    """an array with a frame of padding around (n, rows, cols[, c]) and the view into it"""
-    n, rows, cols = shape[:3]
-    whole = np.full((n, rows + 3, cols + 9) + tuple(shape[3:]), value, dtype)
-    return whole, whole[:, 1:1 + rows, 4:4 + cols]
-
-
 @pytest.mark.parametrize("case", range(len(rc.BODY_CASES)), ids=["%s-%s" % c[:2] for c in rc.BODY_CASES])
 @pytest.mark.parametrize("body", list(BODIES))
 def test_c_bodies_bytes_and_counts_from_the_devices_own_map(problems, body, case):
