@@ -119,6 +119,7 @@ int rship_set_option(rship_ctx* c, int option, int value);
 #define RSHIP_GYRO_BAD_START 5
 #define RSHIP_GYRO_BAD_INPUT 6    /* non-finite timestamp or rate (rates route) */
 #define RSHIP_GYRO_TOO_LARGE 7    /* negative timestamps or more than 2^26 grid points */
+#define RSHIP_GYRO_BAD_TIME_BASE 8 /* first grid sample (first timestamp x rate) >= 2^31, or a timestamp above 2^50 us; told before any launch */
 typedef struct rship_gyro_result {
     double fs, start;      /* grid rate (Hz), time of the first knot (s) */
     uint64_t first_sample; /* grid index of the first knot */

@@ -173,8 +173,13 @@ inline int grid_of(int64_t first, int64_t last, uint32_t count, uint32_t max_kno
     const uint64_t actual_sr_uhz = kUhzInHz * kUsInSec * (uint64_t)count / (uint64_t)(last - first);
     const int rounded_sr_hz = (int)(round((double)actual_sr_uhz / 50. / (double)kUhzInHz) * 50);
     if (rounded_sr_hz <= 0) return RSHIP_GYRO_BAD_RATE;
-    if (first < 0 || last < 0 || last > (int64_t)(1LL << 50)) return RSHIP_GYRO_TOO_LARGE; // unsigned wrap-around in the reference
+    if (first < 0 || last < 0) return RSHIP_GYRO_TOO_LARGE; // unsigned wrap-around in the reference
     const uint64_t sr = (uint64_t)rounded_sr_hz;
+    // The reference keeps the first grid sample, first * sr / 1e6, in an int: from 2^31 on it wraps, and the complaint
+    // that follows speaks of the grid's size when the time base is what is wrong.  first * sr / 1e6 >= 2^31  <=>
+    // first >= ceil(2^31 * 1e6 / sr), by division: the product itself leaves int64 from 2^50 us x 16 kHz on.
+    constexpr uint64_t kFirstSampleEnd = 1ULL << 31;
+    if (last > (int64_t)(1LL << 50) || (uint64_t)first >= (kFirstSampleEnd * kUsInSec + sr - 1) / sr) return RSHIP_GYRO_BAD_TIME_BASE;
     const int first_sample = (int)((uint64_t)(first * rounded_sr_hz) / kUsInSec);
     // samples S with floor(1e6 S / sr) < last  <=>  1e6 S < last sr  <=>  S < ceil(last sr / 1e6)
     const uint64_t end_sample = ((uint64_t)last * sr + kUsInSec - 1) / kUsInSec;

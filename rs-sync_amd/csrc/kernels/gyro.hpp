@@ -13,7 +13,11 @@
 //   * the spline's tridiagonal solve has data-independent pivots (tabulated, gyro_math.hpp) and a
 //     recurrence factor of 2 - sqrt(3) = 0.268 per row in both sweeps: what a row sees of a row k places away
 //     is below 0.268^k, so every thread solves a short run of rows after a warm-up of kSplineWarm rows started
-//     from zero (0.268^64 = 2.5e-37: the warm-up's start cannot be seen in fp64), all runs in parallel.
+//     from zero, all runs in parallel.  0.268^64 = 2.5e-37 cannot be seen in fp64 BESIDE A VALUE OF ORDINARY SIZE.  Where
+//     the data stands still (a camera at rest: equal knots, right-hand sides exactly 0) the sequential solve decays
+//     through 1e-40 .. 1e-300 down to 0, and there the warm-up's start is all there is to see: a run that meets a value
+//     below kSplineCertain is solved again after kSplineWarmLong rows, where 0.268^576 times any coefficient of unit
+//     quaternions is below half the smallest subnormal.  The table is the sequential solve's bit for bit on both paths.
 #pragma once
 
 namespace {
@@ -270,7 +274,10 @@ __global__ __launch_bounds__(256) void gyro_resample_kernel(GyroResampleParams p
 }
 
 // ---- spline table ---------------------------------------------------------------------------------------
-constexpr uint32_t kSplineRun = 32, kSplineWarm = 64;
+constexpr uint32_t kSplineRun = 32, kSplineWarm = 64, kSplineWarmLong = 576;
+// |c'| and |c| are below 8 for knots in [-1, 1]; after kSplineWarm rows the start's share is below 8 x 2.5e-37, which is
+// 2e-6 of an ulp of 1e-14 and less of anything larger
+constexpr double kSplineCertain = 1e-14;
 
 struct SplineParams {
     const double* knots; // [n][4]
@@ -288,19 +295,27 @@ __global__ __launch_bounds__(256) void spline_forward_kernel(SplineParams p) {
     if (s >= p.n) return;
     const uint32_t e = s + kSplineRun < p.n ? s + kSplineRun : p.n;
     const double* y = p.knots + comp;
-    uint32_t i = s > kSplineWarm + 1 ? s - kSplineWarm : 1; // rows 1 .. n-2 carry an equation
-    double c_prev = 0.0;                                      // c'[0] = 0; elsewhere the warm-up start
     if (s == 0) p.cf[comp] = 0.0;
     if (e == p.n) p.cf[4 * (size_t)(p.n - 1) + comp] = 0.0;
     const uint32_t last = e < p.n - 1 ? e : p.n - 1; // exclusive
-    if (i >= last) return;
-    double ym = y[4 * (size_t)(i - 1)], y0 = y[4 * (size_t)i];
-    for (; i < last; ++i) {
-        const double yp = y[4 * (size_t)(i + 1)];
-        c_prev = rs::spline_forward(ym, y0, yp, rs::spline_pivot(p.piv, i - 1), c_prev);
-        if (i >= s) p.cf[4 * (size_t)i + comp] = c_prev;
-        ym = y0;
-        y0 = yp;
+    if ((s > 1 ? s : 1) >= last) return;             // rows 1 .. n-2 carry an equation
+    for (uint32_t warm = kSplineWarm;; warm = kSplineWarmLong) {
+        uint32_t i = s > warm + 1 ? s - warm : 1;
+        const bool from_the_top = i == 1;
+        double c_prev = 0.0;                         // c'[0] = 0; elsewhere the warm-up start
+        double smallest = 1.0;
+        double ym = y[4 * (size_t)(i - 1)], y0 = y[4 * (size_t)i];
+        for (; i < last; ++i) {
+            const double yp = y[4 * (size_t)(i + 1)];
+            c_prev = rs::spline_forward(ym, y0, yp, rs::spline_pivot(p.piv, i - 1), c_prev);
+            if (i >= s) {
+                p.cf[4 * (size_t)i + comp] = c_prev;
+                smallest = fmin(smallest, fabs(c_prev));
+            }
+            ym = y0;
+            y0 = yp;
+        }
+        if (from_the_top || warm == kSplineWarmLong || smallest >= kSplineCertain) break;
     }
 }
 
@@ -311,9 +326,6 @@ __global__ __launch_bounds__(256) void spline_finish_kernel(SplineParams p) {
     const uint32_t e = s + kSplineRun < p.n ? s + kSplineRun : p.n;
     const double* y = p.knots + comp;
     const double* cf = p.cf + comp;
-    // c at the row the backward sweep starts from: the last row (zero), or a forward value far enough away
-    uint32_t j = e + kSplineWarm < p.n - 1 ? e + kSplineWarm : p.n - 1;
-    double c_next = j == p.n - 1 ? 0.0 : cf[4 * (size_t)j];
     auto put = [&](uint32_t i, double yv, double b, double c, double d) {
         double* r64 = p.coef64 + 16 * (size_t)i + comp;
         float* r32 = p.coef32 + 16 * (size_t)i + comp;
@@ -328,15 +340,23 @@ __global__ __launch_bounds__(256) void spline_finish_kernel(SplineParams p) {
         rs::spline_tail(b_prev, d_prev, c_lm, &b, &d);
         put(l, y[4 * (size_t)l], b, 0.0, d);
     }
-    // rows j-1 .. s; row 0 is pinned to zero
-    for (uint32_t i = j; i-- > s;) {
-        const double c_i = i >= 1 ? rs::spline_backward(cf[4 * (size_t)i], rs::spline_pivot(p.piv, i), c_next) : 0.0;
-        if (i < e && i + 1 < p.n) {
-            double b, d;
-            rs::spline_segment(y[4 * (size_t)i], y[4 * (size_t)(i + 1)], c_i, c_next, &b, &d);
-            put(i, y[4 * (size_t)i], b, c_i, d);
+    for (uint32_t warm = kSplineWarm;; warm = kSplineWarmLong) {
+        // c at the row the backward sweep starts from: the last row (zero), or a forward value far enough away
+        const uint32_t j = e + warm < p.n - 1 ? e + warm : p.n - 1;
+        double c_next = j == p.n - 1 ? 0.0 : cf[4 * (size_t)j];
+        double smallest = 1.0;
+        // rows j-1 .. s; row 0 is pinned to zero
+        for (uint32_t i = j; i-- > s;) {
+            const double c_i = i >= 1 ? rs::spline_backward(cf[4 * (size_t)i], rs::spline_pivot(p.piv, i), c_next) : 0.0;
+            if (i <= e && i >= 1) smallest = fmin(smallest, fabs(c_i)); // (row e: the c_next of this run's last segment)
+            if (i < e && i + 1 < p.n) {
+                double b, d;
+                rs::spline_segment(y[4 * (size_t)i], y[4 * (size_t)(i + 1)], c_i, c_next, &b, &d);
+                put(i, y[4 * (size_t)i], b, c_i, d);
+            }
+            c_next = c_i;
         }
-        c_next = c_i;
+        if (j == p.n - 1 || warm == kSplineWarmLong || smallest >= kSplineCertain) break;
     }
 }
 

@@ -1253,7 +1253,7 @@ int spline_from_knots(rship_ctx* c, uint32_t n, double sample_rate) {
 int gyro_status_to_result(rship_ctx* c, const GyroStatus* h, int grid_status, const int64_t* d_ts, rship_gyro_result* out) {
     out->status = RSHIP_GYRO_OK;
     if (h->bad_input) out->status = RSHIP_GYRO_BAD_INPUT;
-    else if (grid_status == RSHIP_GYRO_BAD_RATE || grid_status == RSHIP_GYRO_TOO_LARGE) out->status = grid_status;
+    else if (grid_status == RSHIP_GYRO_BAD_RATE || grid_status == RSHIP_GYRO_TOO_LARGE || grid_status == RSHIP_GYRO_BAD_TIME_BASE) out->status = grid_status;
     else if (h->out_of_order != kNoIndex) {
         int64_t pair[2];
         out->status = RSHIP_GYRO_OUT_OF_ORDER;
@@ -1302,6 +1302,14 @@ int resample_and_solve(rship_ctx* c, const int64_t* d_ts, const double* d_quats,
     return 0;
 }
 
+// A time base past the integer grid (rs::grid_of) is told from the two end timestamps alone: nothing is launched for it.
+bool gyro_time_base_refused(rship_ctx* c, int64_t first, int64_t last, uint32_t n, rship_gyro_result* out) {
+    if (rs::grid_of(first, last, n, kMaxKnots, out) != RSHIP_GYRO_BAD_TIME_BASE) return false;
+    out->status = RSHIP_GYRO_BAD_TIME_BASE;
+    c->n_knots = 0;
+    return true;
+}
+
 } // namespace
 
 int rship_gyro_uniform(rship_ctx* c, const double* quats, uint32_t n, double sample_rate) {
@@ -1317,6 +1325,7 @@ int rship_gyro_uniform(rship_ctx* c, const double* quats, uint32_t n, double sam
 int rship_gyro_timestamped(rship_ctx* c, const int64_t* ts_us, const double* quats, uint32_t n, rship_gyro_result* out) {
     DeviceGuard dev_guard(c);
     if (n < 2) return set_err(c, "gyro: need >= 2 samples");
+    if (gyro_time_base_refused(c, ts_us[0], ts_us[n - 1], n, out)) return 0;
     if (ensure(c, c->g_us, (size_t)n * 8) || ensure(c, c->g_q, (size_t)n * 32) || ensure(c, c->g_status, sizeof(GyroStatus) * 256)) return 1;
     RS_HIP(hipMemcpyAsync(c->g_us.p, ts_us, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
     RS_HIP(hipMemcpyAsync(c->g_q.p, quats, (size_t)n * 32, hipMemcpyHostToDevice, c->stream));
@@ -1435,6 +1444,7 @@ int gyro_rates_integrate(rship_ctx* c, const int32_t axis[3], const double sign[
     for (int k = 0; k < 3; ++k)
         if (axis[k] < 0 || axis[k] > 2) return set_err(c, "gyro: axis out of range");
     if (c->gc_on) return gyro_conditioned_integrate(c, axis, sign, out, status_slot, wait);
+    if (gyro_time_base_refused(c, c->g_first_us, c->g_last_us, n, out)) return 0;
     if (ensure(c, c->g_us, (size_t)n * 8) || ensure(c, c->g_dq, (size_t)n * 32) || ensure(c, c->g_q, (size_t)n * 32) ||
         ensure(c, c->g_status, sizeof(GyroStatus) * kGyroStatusSlots) || ensure(c, c->g_cf, (size_t)(n / kScanSegment + 2) * 64))
         return 1;

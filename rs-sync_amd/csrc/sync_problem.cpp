@@ -605,6 +605,10 @@ void SyncProblemHip::accept_gyro(const rship_gyro_result& r) {
         case RSHIP_GYRO_BAD_KNOT: n_knots_ = 0; panic("set-gyro-quaternions: non-finite sample after interpolation");
         case RSHIP_GYRO_BAD_START: n_knots_ = 0; panic("set-gyro-quaternions: non-finite first timestamp. wtf?");
         case RSHIP_GYRO_TOO_LARGE: n_knots_ = 0; panic("set-gyro-quaternions: resampled grid too large");
+        case RSHIP_GYRO_BAD_TIME_BASE:
+            n_knots_ = 0;
+            panic("set-gyro-quaternions: time base too large: the first timestamp times the sample rate must stay below 2^31 grid samples "
+                  "(and every timestamp below 2^50 us); subtract a common offset from the gyro's and the frames' times");
         default: n_knots_ = 0; panic("set-gyro-quaternions: non-finite sample rate. wtf?");
     }
     if (fs_ != r.fs || start_ != r.start) frames_dirty_ = true;

@@ -223,6 +223,11 @@ int rship_gyro_uniform(rship_ctx* c, const double* quats, uint32_t n, double sam
 
 static int timestamped(rship_ctx* c, const int64_t* ts, const double* quats, uint32_t n, bool bad_input, rship_gyro_result* out) {
     const int grid_status = rs::grid_of(ts[0], ts[n - 1], n, rs::kMaxKnots, out);
+    if (grid_status == RSHIP_GYRO_BAD_TIME_BASE) { // told from the end timestamps alone, before anything else is looked at
+        out->status = grid_status;
+        c->knots.clear(); c->coef.clear(); c->coef64.clear();
+        return 0;
+    }
     uint32_t out_of_order = 0;
     for (uint32_t i = 1; i < n && !out_of_order; ++i)
         if (ts[i - 1] > ts[i]) out_of_order = i;
