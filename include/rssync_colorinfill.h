@@ -1,7 +1,8 @@
 /*
  * rssync_colorinfill.h -- the borders of colour video filled from the neighbouring frames of the call, on the GPU: the
  * infill of rssync_infill.h for every format of rssync_color.h and rssync_color16.h (GRAY8, NV12, I420, RGBA32, GRAY16,
- * P010, P016, I010).  Part of librssync_core.so; a separate header as rssync_colorzoom.h is.  Layout, parameters, defaults,
+ * P010, P016, I010); the 4:2:2 and 4:4:4 formats of rssync_yuv.h have rssync_infillyuv.h.  Part of librssync_core.so; a
+ * separate header as rssync_colorzoom.h is.  Layout, parameters, defaults,
  * output cameras, targets, fills, chroma site, alignment rules, memory placement and errors are those of
  * rssync_color_stabilize and, for the formats RSSYNC_COLOR16_*, rssync_color16_stabilize; params->stab.zoom is read (one
  * zoom for the call).  Both cameras, both filters, any output size, host or device memory, pitched or not.

@@ -10,7 +10,7 @@
  * (params->stab.filter), host and device memory, the chunking and the overlap rule.  See rssync_color.h, and
  * rssync_color16.h for the samples in 16-bit containers.
  *
- * Formats.  These numbers go through this header's functions and, with a zoom per frame, through rssync_zoomyuv.h's alone:
+ * Formats.  These numbers go through this header's functions, rssync_zoomyuv.h's (a zoom per frame) and rssync_infillyuv.h's alone:
  * rssync_color_*, rssync_color16_*, rssync_colorzoom_* and rssync_colorinfill_* turn them away, and these functions turn
  * every other number away.  Row widths are in bytes; every plane has H rows.
  *   format                planes              row bytes        sample and container
@@ -53,8 +53,8 @@
  * ("pitch"); a fill outside the format's range ("fill"); a chroma site outside its enum ("chroma_site"); a plane other than
  * 0 or 1 asked of rssync_yuv_map ("plane").  The problem stays usable after an error.
  *
- * Not here: the infill (rssync_colorinfill.h) for these formats; packed 4:2:2 (YUY2, UYVY, v210); 4:4:4 at 16 bits
- * beyond I410.  A zoom per frame: rssync_zoomyuv.h.
+ * Not here: packed 4:2:2 (YUY2, UYVY, v210); 4:4:4 at 16 bits beyond I410.  A zoom per frame: rssync_zoomyuv.h.  The
+ * borders filled from neighbouring frames: rssync_infillyuv.h.
  */
 #ifndef RSSYNC_YUV_H
 #define RSSYNC_YUV_H

@@ -70,6 +70,7 @@
 #include "colorinfill_hip.h"
 #include "yuv_hip.h"
 #include "zoomyuv_hip.h"
+#include "infillyuv_hip.h"
 #include "device_math.hpp"
 #include "sync_math.hpp"
 #include "lens_math.hpp"
@@ -116,6 +117,7 @@ using rs::f4;
 #include "kernels/zoomyuv.hpp"
 #include "kernels/infill.hpp"
 #include "kernels/colorinfill.hpp"
+#include "kernels/infillyuv.hpp"
 
 // ===========================================================================
 // host side of the C-ABI
@@ -5269,6 +5271,84 @@ int rship_colorinfill_frames(rship_ctx* c, const rship_color_image* in, uint32_t
         D.src0 = dev_in ? 0 : C.src0;
         for (int k = 0; dev_in && k < np; ++k) D.C.src[k] = in->plane[k];
         format_launch<DonorFamily>(c, cfg->format, L.camera, L.filter, L.out_width, L.out_height, C.cnt, D);
+        RS_HIP(hipGetLastError());
+        return 0;
+    });
+}
+
+} // extern "C"
+
+// ===========================================================================
+// infill of 4:2:2 and 4:4:4 frames (kernels/infillyuv.hpp; declared in infillyuv_hip.h, called by infillyuv_api.cpp).
+// rship_colorinfill_frames with the checks, the planes and the grid of rship_yuv_frames: rows_c is 0 for these formats, so
+// donor_rows_kernel builds the luma's tables alone, and a 4:2:2 chroma camera reads them.
+
+namespace {
+
+template <int C, int F> struct LendI422 { static constexpr auto kernel = lend422_8_kernel<C, false, F>; };
+template <int C, int F> struct LendNv16 { static constexpr auto kernel = lend422_8_kernel<C, true, F>; };
+template <int C, int F> struct LendI444 { static constexpr auto kernel = lend444_8_kernel<C, F>; };
+template <int C, int F> struct LendI210 { static constexpr auto kernel = lend422_16_kernel<C, false, 0, F>; };
+template <int C, int F> struct LendP210 { static constexpr auto kernel = lend422_16_kernel<C, true, 6, F>; };
+template <int C, int F> struct LendP216 { static constexpr auto kernel = lend422_16_kernel<C, true, 0, F>; };
+template <int C, int F> struct LendI410 { static constexpr auto kernel = lend444_16_kernel<C, F>; };
+
+// yuv_launch with a candidate loop
+void lend_launch(rship_ctx* c, int format, int camera, int filter, uint32_t ow, uint32_t oh, uint32_t cnt, const LendArgs& L) {
+    const uint32_t gw = color_is_422(format) ? ow / 2 : ow;
+    const dim3 grid((gw + kRectTW - 1) / kRectTW, (oh + kRectTH - 1) / kRectTH, cnt);
+    switch (format) {
+    case 32: camfilt_launch<LendI422>(c, camera, filter, grid, L); break;
+    case 33: camfilt_launch<LendNv16>(c, camera, filter, grid, L); break;
+    case 34: camfilt_launch<LendI444>(c, camera, filter, grid, L); break;
+    case 48: camfilt_launch<LendI210>(c, camera, filter, grid, L); break;
+    case 49: camfilt_launch<LendP210>(c, camera, filter, grid, L); break;
+    case 50: camfilt_launch<LendP216>(c, camera, filter, grid, L); break;
+    case 51: camfilt_launch<LendI410>(c, camera, filter, grid, L); break;
+    }
+}
+
+} // namespace
+
+extern "C" {
+
+int rship_infillyuv_frames(rship_ctx* c, const rship_color_image* in, uint32_t n_frames, const double* frame_times, const double* targets,
+                           const rship_color_cfg* cfg, const rship_color_image* out, uint64_t* n_outside, int32_t radius,
+                           uint64_t* n_borrowed, size_t budget_bytes) {
+    DeviceGuard dev_guard(c);
+    if (yuv_check(c, cfg)) return 1;
+    if (radius < 0 || radius > rs::kInfillMaxRadius) return set_err(c, "infillyuv: radius must be 0 .. 8");
+    if (!in || !out || !frame_times) return set_err(c, "color: null pointer");
+    if (!n_frames) return 0;
+    const rship_stabilize_cfg L = color_luma(cfg);
+    rs::FramePlane planes[3];
+    const int np = color_planes(cfg->format, L.width, L.height, planes);
+    LendArgs A{};
+    DonorArgs& D = A.D;
+    D.n_frames = n_frames;
+    D.radius = radius;
+    // (the counts: filled plane 0, filled chroma, borrowed plane 0, borrowed chroma)
+    uint64_t* const pairs[2] = {n_outside, n_borrowed};
+    return color_call<DonorRowsArgs>(c, in, n_frames, frame_times, targets, cfg, out, budget_bytes, (uint32_t)radius, true, pairs, 2,
+                                     [&](const FrameChunk& C, DonorRowsArgs& R, ColorLaunch& K, bool dev_in) -> int {
+        R.times = (const double*)c->rect_times.p;
+        R.times_c = R.times + n_frames;
+        R.targets = (const double*)c->stab_targets.p;
+        R.f0 = C.f0;
+        R.n_frames = n_frames;
+        R.radius = radius;
+        hipLaunchKernelGGL(donor_rows_kernel, dim3(color_rows_blocks(R.rows, R.rows_c), 2 * (uint32_t)radius + 1, C.cnt), dim3(256), 0, c->stream, R);
+        RS_HIP(hipGetLastError());
+        D.C = K.A;
+        D.fill_y = K.fill16_y;
+        D.fill_uv = K.fill16_uv;
+        D.borrowed = D.C.outside + 2 * (size_t)n_frames;
+        D.borrowed_c = D.C.outside + 3 * (size_t)n_frames;
+        D.f0 = C.f0;
+        // (device frames: the kernels read the neighbours in place, from frame 0 of the call)
+        D.src0 = dev_in ? 0 : C.src0;
+        for (int k = 0; dev_in && k < np; ++k) D.C.src[k] = in->plane[k];
+        lend_launch(c, cfg->format, L.camera, L.filter, L.out_width, L.out_height, C.cnt, A);
         RS_HIP(hipGetLastError());
         return 0;
     });

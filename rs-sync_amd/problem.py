@@ -882,6 +882,19 @@ class SyncProblem:
         from . import colorzoom
         return colorzoom.dynamic_zoom_color(self, fmt, width, height, lens, frame_times, delay, lo, hi, window, **params)
 
+    def stabilize_yuv_infilled(self, fmt, frames, frame_times, lens, delay, radius, **params):
+        """stabilize_yuv with the borders of every plane taken from up to `radius` neighbouring frames of the call on each
+        side (include/rssync_infillyuv.h, rssync_amd.infillyuv) -> (planes in the layout of `frames`, n_outside (n, 2),
+        n_borrowed (n, 2)).  params: targets, out_size, out, n_borrowed, chroma_site, fills, sigma, zoom, camera, out_camera,
+        iterations, fill, filter."""
+        from . import infillyuv
+        return infillyuv.stabilize_yuv_infilled(self, fmt, frames, frame_times, lens, delay, radius, **params)
+
+    def stabilize_yuv_infilled_budget(self, fmt, frames, frame_times, lens, delay, radius, budget_bytes, **params):
+        """stabilize_yuv_infilled through the internal launcher with a device budget for its chunk slots (tests)."""
+        from . import infillyuv
+        return infillyuv.stabilize_yuv_infilled_budget(self, fmt, frames, frame_times, lens, delay, radius, budget_bytes, **params)
+
     def stabilize_yuv_zoomed(self, fmt, frames, frame_times, lens, delay, zooms, **params):
         """stabilize_yuv with one zoom per frame (include/rssync_zoomyuv.h, rssync_amd.zoomyuv) -> (planes in the layout of
         `frames`, n_outside (n, 2)).  params: targets, out_size, out, chroma_site, fills, sigma, camera, out_camera,
