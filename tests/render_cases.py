@@ -11,14 +11,18 @@ motions of tests/warp_cases.py.  Helpers only: numpy, warp_cases and the restate
   fits     FIT_CASES / STRENGTH_CASES: zoom and strength fits whose three float64 readings agree in every frame
   infill   INFILL_CASES and the composition of a frame from per-candidate maps (compose_plane)
   checks   check_map, padded and u32, which tests/test_gpu_yuv_lenses.py shares with tests/test_gpu_render_lenses.py
+  formats  the colour front's formats with their noise planes, fills and numpy samplers (color_frames, color_fills,
+           color_sample_plane, color_plane_fill), which tests/test_gpu_infill_lenses.py shares with it
 """
 import functools
 
 import numpy as np
 
+import color16_reference as c16
 import color_reference as cr
 import infill_reference as ir
 import limit_reference as lr
+import resample_reference as q
 import stabilize_reference as sr
 import warp_cases as wc
 import zoom_reference as zr
@@ -180,6 +184,62 @@ def noise16(depth, n=N_FRAMES, seed=29):
     for a in d.values():
         a.setflags(write=False)
     return d
+
+
+# ---- the colour front's formats: their noise planes, fills and numpy samplers ------------------------------------------------
+# (shared by tests/test_gpu_render_lenses.py and tests/test_gpu_infill_lenses.py)
+GRAY8, NV12, I420, RGBA32 = 0, 1, 2, 3
+GRAY16, P010, P016, I010 = 16, 17, 18, 19
+COLOR_SIBLING = {GRAY16: GRAY8, P010: NV12, P016: NV12, I010: I420}
+COLOR_DEPTH = {GRAY8: 8, NV12: 8, I420: 8, RGBA32: 8, GRAY16: 16, P010: 10, P016: 16, I010: 10}
+FILLS8 = (7, 99, 200, 31)
+FILLS16 = {10: (70, 300, 900), 16: (700, 30000, 60000)}               # sample values
+
+
+def color_frames(fmt, sub=slice(None)):
+    """the noise planes of a format as the calls take them (stored words) -> frames argument"""
+    if fmt in COLOR_SIBLING:
+        d = noise16(COLOR_DEPTH[fmt])
+        y, u, v, uv = (c16.pack(fmt, (d[k][sub],))[0] for k in ("y", "u", "v", "uv"))
+    else:
+        d = noise8()
+        y, u, v, uv = (d[k][sub] for k in ("y", "u", "v", "uv"))
+    return {GRAY8: y, NV12: (y, uv), I420: (y, u, v), RGBA32: noise8()["rgba"][sub]}[COLOR_SIBLING.get(fmt, fmt)]
+
+
+def color_fills(fmt):
+    f = FILLS16[COLOR_DEPTH[fmt]] if fmt in COLOR_SIBLING else FILLS8
+    return f if fmt == RGBA32 else f[:1] if fmt in (GRAY8, GRAY16) else f[:3]
+
+
+def as_tuple(x):
+    return tuple(x) if isinstance(x, (tuple, list)) else (x,)
+
+
+def color_sample_plane(fmt, k, words, m, fill, filter):
+    """plane k of a format (stored words) through the numpy sampler on a map -> (stored words, samples filled): the 8-bit
+    restatements, and for the 16-bit formats the same arithmetic on the sample values"""
+    pairs = words.ndim == 3 and words.shape[-1] == 2
+    if fmt == RGBA32:
+        return (cr.sample_rgba if filter == 0 else q.sample_bicubic_rgba)(words, m, fill)
+    if fmt not in COLOR_SIBLING:
+        if pairs:
+            return (cr.sample_pairs if filter == 0 else q.sample_bicubic_pairs)(words, m, fill)
+        return (sr.sample if filter == 0 else q.sample_bicubic)(words, m, fill)
+    if filter == 1:
+        return q.sample_bicubic_pairs16(fmt, words, m, fill) if pairs else q.sample_bicubic16(fmt, words, m, fill)
+    (vals,) = c16.unpack(fmt, (words,))
+    out, n = c16.sample_pairs16(vals, m, fill) if pairs else c16.sample16(vals, m, fill)
+    return c16.pack(fmt, (out,))[0], n
+
+
+def color_plane_fill(fmt, k, fills):
+    """the fill argument of plane k's sampler"""
+    if fmt == RGBA32:
+        return fills
+    if k == 0:
+        return fills[0]
+    return (fills[1], fills[2]) if COLOR_SIBLING.get(fmt, fmt) == NV12 else fills[k]
 
 
 # ---- fits ---------------------------------------------------------------------------------------------------------------

@@ -24,24 +24,20 @@ import numpy as np
 import pytest
 import torch  # noqa: F401  (imported before the library: torch ships its own HIP runtime, tests/test_gpu_parity.py)
 
-import color16_reference as c16
 import color_reference as cr
 import infill_reference as ir
 import render_cases as rc
-import resample_reference as q
 import stabilize_reference as sr
 import warp_cases as wc
 
 pytestmark = pytest.mark.gpu
 
-GRAY8, NV12, I420, RGBA32 = 0, 1, 2, 3
-GRAY16, P010, P016, I010 = 16, 17, 18, 19
+GRAY8, NV12, I420, RGBA32 = rc.GRAY8, rc.NV12, rc.I420, rc.RGBA32
+GRAY16, P010, P016, I010 = rc.GRAY16, rc.P010, rc.P016, rc.I010
 FORMATS = (GRAY8, NV12, I420, RGBA32, P010, I010, GRAY16)            # section d
 BODIES = {"yuv8-nv12": NV12, "yuv8-i420": I420, "rgba8": RGBA32, "yuv16-p010": P010, "yuv16-p016": P016, "yuv16-i010": I010,
           "gray16": GRAY16}                                           # section c
-SIBLING = {GRAY16: GRAY8, P010: NV12, P016: NV12, I010: I420}
-FILLS8 = (7, 99, 200, 31)
-FILLS16 = {10: (70, 300, 900), 16: (700, 30000, 60000)}               # sample values
+SIBLING, FILLS8, FILLS16 = rc.COLOR_SIBLING, rc.FILLS8, rc.FILLS16
 
 
 def _problem(gyro):
@@ -61,54 +57,8 @@ def problems(built):
 _u32, _check_map, _padded = rc.u32, rc.check_map, rc.padded
 
 
-def _depth(fmt):
-    return {GRAY8: 8, NV12: 8, I420: 8, RGBA32: 8, GRAY16: 16, P010: 10, P016: 16, I010: 10}[fmt]
-
-
-def _input(fmt, sub=slice(None)):
-    """the noise planes of a format as the calls take them (stored words) -> frames argument"""
-    if fmt in SIBLING:
-        d = rc.noise16(_depth(fmt))
-        y, u, v, uv = (c16.pack(fmt, (d[k][sub],))[0] for k in ("y", "u", "v", "uv"))
-    else:
-        d = rc.noise8()
-        y, u, v, uv = (d[k][sub] for k in ("y", "u", "v", "uv"))
-    return {GRAY8: y, NV12: (y, uv), I420: (y, u, v), RGBA32: rc.noise8()["rgba"][sub]}[SIBLING.get(fmt, fmt)]
-
-
-def _fills(fmt):
-    f = FILLS16[_depth(fmt)] if fmt in SIBLING else FILLS8
-    return f if fmt == RGBA32 else f[:1] if fmt in (GRAY8, GRAY16) else f[:3]
-
-
-def _as_tuple(x):
-    return tuple(x) if isinstance(x, (tuple, list)) else (x,)
-
-
-def _sample_plane(fmt, k, words, m, fill, filter):
-    """plane k of a format (stored words) through the numpy sampler on a map -> (stored words, samples filled): the 8-bit
-    restatements, and for the 16-bit formats the same arithmetic on the sample values"""
-    pairs = words.ndim == 3 and words.shape[-1] == 2
-    if fmt == RGBA32:
-        return (cr.sample_rgba if filter == 0 else q.sample_bicubic_rgba)(words, m, fill)
-    if fmt not in SIBLING:
-        if pairs:
-            return (cr.sample_pairs if filter == 0 else q.sample_bicubic_pairs)(words, m, fill)
-        return (sr.sample if filter == 0 else q.sample_bicubic)(words, m, fill)
-    if filter == 1:
-        return q.sample_bicubic_pairs16(fmt, words, m, fill) if pairs else q.sample_bicubic16(fmt, words, m, fill)
-    (vals,) = c16.unpack(fmt, (words,))
-    out, n = c16.sample_pairs16(vals, m, fill) if pairs else c16.sample16(vals, m, fill)
-    return c16.pack(fmt, (out,))[0], n
-
-
-def _plane_fill(fmt, k, fills):
-    """the fill argument of plane k's sampler"""
-    if fmt == RGBA32:
-        return fills
-    if k == 0:
-        return fills[0]
-    return (fills[1], fills[2]) if SIBLING.get(fmt, fmt) == NV12 else fills[k]
+# the formats' noise planes, fills and numpy samplers: shared with tests/test_gpu_infill_lenses.py
+_input, _fills, _as_tuple, _sample_plane, _plane_fill = rc.color_frames, rc.color_fills, rc.as_tuple, rc.color_sample_plane, rc.color_plane_fill
 
 
 # a -----------------------------------------------------------------------------------------------------------------------
